@@ -1,8 +1,16 @@
 """Benchmark of the spectrogram-enhancement hot path on 1..N MI355X GPUs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR]
+    python bench.py --full [--no-cpu-baseline] [--no-stages] ...
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value,
+unit, higher_is_better, dtype, ms_per_step, config): nothing else runs. --full adds the
+roofline, stages, cpu_baseline and accuracy legs described below (null in a plain run).
+--dump-outputs DIR writes what the last timed step returned (DIR/reconstructions.npy,
+float32; a fixed seeded sample of the shots when the batch exceeds DUMP_MAX_SHOTS). The
+inputs are seeded, so two builds run with the same arguments compare output for output.
 
 BASELINE.json's metric is "spectrograms/s (STFT+VAE-denoise fwd) ... PSNR vs CPU ref":
 the end-to-end inference stream of SURVEY.md §8(d) C5, per GPU. One step = one batch of
@@ -23,7 +31,7 @@ The batch splits over --streams HIP streams (default 2) with staggered chains.
 Shots shard across ranks (each rank owns its B shots; no collective in the data path;
 weak scaling); value = all ranks' spectrograms / max-over-ranks wall time.
 
-Rank 0 prints ONE JSON line with, besides the contract fields:
+Rank 0 prints ONE JSON line with, besides the contract fields (the rest under --full):
   roofline      the dominant kernel of a step: the autoencoder layer launch with the largest
                 measured time (HIP events around every launch, on its stream). Its bound is
                 whichever floor is higher: algorithmic HBM bytes (activations read once and
@@ -615,6 +623,28 @@ def throughput(world: int, batch: int, steps: int, elapsed: float) -> float:
     return world * batch * steps / elapsed
 
 
+# ------------------------------------------------------------------ --dump-outputs
+DUMP_MAX_SHOTS = 512  # x 128 x 128 float32 = 32 MiB per file (one file per rank)
+
+
+def dump_outputs(dirname, Y, rank=0):
+    """Write the reconstructions the last timed step returned (``Y``: the step's tensor, or
+    its per-stream slices in shot order) as float32 [n, 128, 128, 1]: every shot of a batch
+    up to DUMP_MAX_SHOTS, else the sorted shots of a fixed seeded draw (the same shots in
+    every run with the same --batch). Rank 0 writes reconstructions.npy, rank r > 0
+    reconstructions_rank<r>.npy (its own shard)."""
+    import torch
+    if isinstance(Y, (list, tuple)):
+        Y = torch.cat(list(Y))
+    n = Y.shape[0]
+    if n > DUMP_MAX_SHOTS:
+        pick = np.sort(np.random.default_rng(20240).choice(n, DUMP_MAX_SHOTS, replace=False))
+        Y = Y.index_select(0, torch.as_tensor(pick, device=Y.device))
+    os.makedirs(dirname, exist_ok=True)
+    name = "reconstructions.npy" if rank == 0 else f"reconstructions_rank{rank}.npy"
+    np.save(os.path.join(dirname, name), Y.float().cpu().numpy())
+
+
 # ------------------------------------------------------------------ GPU
 def main():
     ap = argparse.ArgumentParser()
@@ -627,7 +657,15 @@ def main():
     ap.add_argument("--no-stages", action="store_true")
     ap.add_argument("--streams", type=int, default=2,
                     help="HIP streams the batch is split over (staggered chains; 1 = serial)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baseline, the per-layer roofline, the C2/C3/C4/"
+                         "host-stream stages and the accuracy check (a plain run only times "
+                         "the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's reconstructions to DIR/*.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -637,7 +675,7 @@ def main():
     # (the other ranks wait in the process-group rendezvous), so a scaling line at N > 1
     # carries the same baseline as N = 1
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.cpu_shots)
 
     import torch
@@ -718,9 +756,49 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0, dist if use_dist else None, dev)
+
+    # the last timed step's reconstructions, before any other leg reuses the engines' buffers
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, rank)
+    del last
+
+    res = {
+        "metric": METRIC,
+        "value": throughput(world, B, args.steps, elapsed),
+        "unit": "spectrograms/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "fp16",
+        "full": args.full,
+        "data": "synthetic (seeded plasma chirps + noise + drift, generated on device, fp16); "
+                "autoencoder weights trained on synthetic C4 data by the CPU oracle "
+                "(tests/golden/ae_c4_trained.npz; no reference checkpoint exists)",
+        "config": {"workload": "BASELINE config 5 per GPU: end-to-end STFT -> SVD -> "
+                               "autoencoder-denoise inference stream, 16,512-sample fp16 "
+                               "shots -> specgr 128x128 (256 hann / hop 128) -> "
+                               "denoiseSignal default -> 3-layer conv AE (16/32/64, 5x5) "
+                               "fp16 forward -> fp16 reconstructions (32,768 B per shot)",
+                   "shots_per_step": B, "shots_per_launch": Hs, "samples": L5, "stft_dtype": "fp32",
+                   "svd_dtype": "fp32 (fp64 small algebra)", "ae_dtype": "fp16",
+                   "parallelism": f"shot-sharded x{world}", "streams_per_gpu": NS},
+    }
+    if not args.full:  # a plain run ends here: the legs below are --full's
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            res.update({"roofline": None, "cpu_baseline": None, "psnr_db": None,
+                        "accuracy": None, "stages": None})
+            print(json.dumps(res))
+        return
 
     # ---- dominant kernel: conv_fwd_kernel, every conv launch bracketed by HIP events on
     # the stream it is launched on ----
@@ -898,29 +976,7 @@ def main():
     if rank != 0:
         return
 
-    res = {
-        "metric": METRIC,
-        "value": throughput(world, B, args.steps, elapsed),
-        "unit": "spectrograms/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "fp16",
-        "data": "synthetic (seeded plasma chirps + noise + drift, generated on device, fp16); "
-                "autoencoder weights trained on synthetic C4 data by the CPU oracle "
-                "(tests/golden/ae_c4_trained.npz; no reference checkpoint exists)",
-        "config": {"workload": "BASELINE config 5 per GPU: end-to-end STFT -> SVD -> "
-                               "autoencoder-denoise inference stream, 16,512-sample fp16 "
-                               "shots -> specgr 128x128 (256 hann / hop 128) -> "
-                               "denoiseSignal default -> 3-layer conv AE (16/32/64, 5x5) "
-                               "fp16 forward -> fp16 reconstructions (32,768 B per shot)",
-                   "shots_per_step": B, "shots_per_launch": Hs, "samples": L5, "stft_dtype": "fp32",
-                   "svd_dtype": "fp32 (fp64 small algebra)", "ae_dtype": "fp16",
-                   "parallelism": f"shot-sharded x{world}", "streams_per_gpu": NS},
+    res.update({
         "roofline": {k: dom[k] for k in ("bound", "achieved", "peak", "unit", "frac",
                                            "traffic")} |
                     {"layer": f"{dom['layer']} launch of the autoencoder forward",
@@ -936,7 +992,7 @@ def main():
         "psnr_db": accuracy["psnr_db"] if accuracy else None,
         "accuracy": accuracy,
         "stages": stages,
-    }
+    })
     print(json.dumps(res))
 
 
