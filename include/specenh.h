@@ -1,7 +1,8 @@
 /*
  * specenh.h — C-ABI of the MI355X-native spectrogram-enhancement hot path.
  *
- * libspecenh.so (hipcc, gfx950) exports exactly these symbols. Signatures use
+ * libspecenh.so (hipcc, gfx950) exports exactly these symbols, plus the complex STFT /
+ * inverse STFT entry points declared in specenh_stft_complex.h. Signatures use
  * plain pointers, sizes and a HIP stream handle (void*, may be NULL = default
  * stream); no torch types. Device pointers must be on the current HIP device.
  * Every entry point returns 0 on success or a negative SPECENH_E* code; the text

@@ -1344,7 +1344,7 @@ hipError_t launch_team(const StftArgs& a, long long batch, void* workspace, hipS
 
 using namespace specenh;
 
-struct specenh_stft_plan;
+#include "stft_plan.hpp"
 
 namespace specenh {
 // Cross-spectrum amplitude |Pxy| [batch][N/2 + 1][T] of the signal pairs (x[b], y[b]) on the
@@ -1356,17 +1356,6 @@ int stft_csd_amplitude(const specenh_stft_plan* plan, const float* x, const floa
                        long long batch, long long length, long long x_stride, long long y_stride,
                        float* out, hipStream_t stream, bool* launched);
 }  // namespace specenh
-
-struct specenh_stft_plan {
-  int nperseg, noverlap, hop;
-  double fs, eps, scale;
-  int scaling, detrend;
-  int device;
-  float* d_window;
-  float2* d_twiddle;
-  double dc_alpha, dc_beta;  // DC coefficients from the fp32 window (StftArgs)
-  double* d_dc;              // c_n = w_n - alpha - beta (n - kmid), fp64
-};
 
 extern "C" {
 
@@ -1447,10 +1436,21 @@ int specenh_stft_plan_create(specenh_stft_plan** plan, int nperseg, int noverlap
   p->scale = scaling == SPECENH_SCALING_DENSITY ? 1.0 / (fs * s2) : 1.0 / (s1 * s1);
   p->dc_alpha = dc_alpha;
   p->dc_beta = dc_beta;
+  p->win_sum = s1;
+  p->win_sumsq = s2;
   hipError_t e = hipGetDevice(&p->device);
   if (e == hipSuccess) e = hipMalloc(&p->d_window, N * sizeof(float));
   if (e == hipSuccess) e = hipMalloc(&p->d_twiddle, tw.size() * sizeof(float2));
   if (e == hipSuccess) e = hipMalloc(&p->d_dc, N * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc(&p->d_tw_nat, N * sizeof(float2));
+  if (e == hipSuccess) {  // natural-order twiddles of the complex STFT / inverse STFT
+    std::vector<float2> nat(N);
+    for (int i = 0; i < N; ++i) {
+      ct::CS cs = ct::cossin_frac(i, N);
+      nat[i] = make_float2(float(cs.c), float(-cs.s));
+    }
+    e = hipMemcpy(p->d_tw_nat, nat.data(), N * sizeof(float2), hipMemcpyHostToDevice);
+  }
   if (e == hipSuccess) {
     std::vector<double> dc(N);
     for (int i = 0; i < N; ++i) dc[i] = (double(win[i]) - dc_alpha) - dc_beta * (i - 0.5 * (N - 1));
@@ -1462,6 +1462,7 @@ int specenh_stft_plan_create(specenh_stft_plan** plan, int nperseg, int noverlap
     (void)hipFree(p->d_window);
     (void)hipFree(p->d_twiddle);
     (void)hipFree(p->d_dc);
+    (void)hipFree(p->d_tw_nat);
     delete p;
     return set_error(SPECENH_EHIP, std::string("plan allocation: ") + hipGetErrorString(e));
   }
@@ -1474,6 +1475,7 @@ int specenh_stft_plan_destroy(specenh_stft_plan* plan) {
   (void)hipFree(plan->d_window);
   (void)hipFree(plan->d_twiddle);
   (void)hipFree(plan->d_dc);
+  (void)hipFree(plan->d_tw_nat);
   delete plan;
   return SPECENH_OK;
 }

@@ -5,6 +5,8 @@ Reference-compatible entry points (same names/arguments as the reference):
   specenh.svd           : omega, denoiseSignal, computeSignal
   specenh.strips        : patch, unpatch, reshape
   specenh.keras         : layers / Model / compile / fit / predict / save / load_model
+scipy-compatible return path (complex STFT, gain mask, inverse STFT):
+  specenh.signal        : stft, istft (numpy); specenh.stft.stft / istft (device tensors)
 Device fast paths: specgr_batch, denoise_batch, cross_spectrogram_batch, and
 specenh.autograd (differentiable Conv2D / Conv2DTranspose / MaxPooling2D / BCE).
 Every one of them reaches the HIP kernels through the ``torch.ops.specenh`` operators

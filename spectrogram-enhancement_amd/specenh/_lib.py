@@ -38,6 +38,8 @@ STFT_EXACT = 8  # one frame per FFT (include/specenh.h SPECENH_STFT_EXACT)
 
 DETREND = {False: 0, None: 0, "constant": 1, "c": 1, "linear": 2, "l": 2}
 SCALING = {"density": 0, "spectrum": 1}
+BOUNDARY_NONE = 0
+BOUNDARY_ZEROS = 1
 
 
 class ExtensionNotLoaded(RuntimeError):
@@ -175,6 +177,19 @@ SIGNATURES = {
                                          _c.c_int, _c.c_void_p, _c.c_void_p]),
 }
 
+# the complex STFT / inverse STFT entry points; must match include/specenh_stft_complex.h
+SIGNATURES_STFT_COMPLEX = {
+    "specenh_stft_complex_frames": (_c.c_longlong, [_c.c_longlong, _c.c_int, _c.c_int, _c.c_int,
+                                                    _c.c_int]),
+    "specenh_stft_complex": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_longlong, _c.c_longlong,
+                                        _c.c_longlong, _c.c_void_p, _c.c_int, _c.c_int,
+                                        _c.c_void_p]),
+    "specenh_istft_length": (_c.c_longlong, [_c.c_longlong, _c.c_int, _c.c_int, _c.c_int]),
+    "specenh_istft": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_longlong,
+                                 _c.c_longlong, _c.c_void_p, _c.c_longlong, _c.c_int,
+                                 _c.c_void_p]),
+}
+
 
 def lib():
     """Load (once) and return the ctypes handle; raise ExtensionNotLoaded on failure."""
@@ -193,7 +208,7 @@ def lib():
         except OSError as e:
             raise ExtensionNotLoaded(f"failed to load {LIB_PATH}: {e}") from e
         dev_build = bool(os.environ.get("SPECENH_LIB"))
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in {**SIGNATURES, **SIGNATURES_STFT_COMPLEX}.items():
             if dev_build and not hasattr(h, name):
                 continue  # an older revision's build for an A/B run (tools/build_rev_lib.sh)
             fn = getattr(h, name)

@@ -134,6 +134,99 @@ _op(f"stft_psd_out(Tensor x, {_STFT_ARGS}, Tensor(a!) out) -> ()", _stft_out,
     lambda *a: None)
 
 
+# ---------------------------------------------------------------- complex STFT / inverse
+def _cx_frames(length, nperseg, noverlap, boundary, padded):
+    """specenh_stft_complex_frames (scipy.signal.stft's frame count), also on symbolic sizes."""
+    hop = nperseg - noverlap
+    ext = length + (nperseg if boundary else 0)
+    nadd = ((-(ext - nperseg)) % hop) % nperseg if padded else 0
+    return (ext + nadd - nperseg) // hop + 1
+
+
+def _istft_len(frames, nperseg, noverlap, boundary):
+    return (nperseg - noverlap) * (frames - 1) + (0 if boundary else nperseg)
+
+
+def _stft_complex_out(x, nperseg, noverlap, window, fs, scaling, detrend, boundary, padded, out):
+    from . import stft
+    if x.dim() != 2 or x.stride(1) != 1 or x.dtype != torch.float32:
+        raise ValueError("x must be float32 [batch, length] with unit stride along length")
+    if boundary not in (_lib.BOUNDARY_NONE, _lib.BOUNDARY_ZEROS):
+        raise NotImplementedError("boundary must be None or 'zeros' on the GPU path")
+    B, L = x.shape
+    if L < nperseg:
+        raise ValueError("signal shorter than nperseg")
+    shape = (B, nperseg // 2 + 1, _cx_frames(L, nperseg, noverlap, boundary, padded))
+    if tuple(out.shape) != shape or out.dtype != torch.complex64 or not out.is_contiguous():
+        raise ValueError(f"out must be contiguous complex64 {shape}")
+    plan = stft.get_plan_key(x.device, nperseg, noverlap, window, fs, scaling, detrend, 0.0)
+    _lib.check(_lib.lib().specenh_stft_complex(
+        plan.handle, _vp(x), B, L, x.stride(0) if B > 1 else L, _vp(out), int(boundary),
+        int(padded), _st(x)), "stft_complex")
+
+
+def _stft_complex(x, nperseg, noverlap, window, fs, scaling, detrend, boundary, padded):
+    if noverlap >= nperseg:
+        raise ValueError("noverlap must be less than nperseg.")
+    out = torch.empty((x.shape[0], nperseg // 2 + 1,
+                       _cx_frames(x.shape[1], nperseg, noverlap, boundary, padded)),
+                      dtype=torch.complex64, device=x.device)
+    _stft_complex_out(x, nperseg, noverlap, window, fs, scaling, detrend, boundary, padded, out)
+    return out
+
+
+def _istft_out(Z, gain, nperseg, noverlap, window, fs, scaling, boundary, out):
+    from . import stft
+    if Z.dim() != 3 or Z.dtype != torch.complex64 or not Z.is_contiguous() or Z.is_conj():
+        raise ValueError("Z must be contiguous complex64 [batch, F, T]")
+    B, F, T = Z.shape
+    if nperseg != 2 * (F - 1):
+        raise ValueError("nperseg must equal 2*(F - 1) of the one-sided spectrogram")
+    rows = 0
+    if gain is not None:
+        if (gain.dim() != 3 or gain.dtype != torch.float32 or not gain.is_contiguous()
+                or gain.device != Z.device or gain.shape[0] != B or gain.shape[2] != T
+                or gain.shape[1] not in (F, F - 1)):
+            raise ValueError(f"gain must be contiguous float32 [{B}, {F} or {F - 1}, {T}] on Z's "
+                             "device")
+        rows = gain.shape[1]
+    n = _istft_len(T, nperseg, noverlap, boundary)
+    if (out.dim() != 2 or out.shape[0] != B or out.shape[1] != n or out.dtype != torch.float32
+            or out.stride(1) != 1 or out.device != Z.device):
+        raise ValueError(f"out must be float32 [{B}, {n}] with unit stride along samples")
+    plan = stft.get_plan_key(Z.device, nperseg, noverlap, window, fs, scaling, 0, 0.0)
+    _lib.check(_lib.lib().specenh_istft(
+        plan.handle, _vp(Z), _vp(gain), rows, B, T, _vp(out), out.stride(0) if B > 1 else n,
+        int(bool(boundary)), _st(Z)), "istft")
+
+
+def _istft(Z, gain, nperseg, noverlap, window, fs, scaling, boundary):
+    if noverlap >= nperseg:
+        raise ValueError("noverlap must be less than nperseg.")
+    out = torch.empty((Z.shape[0], _istft_len(Z.shape[2], nperseg, noverlap, boundary)),
+                      dtype=torch.float32, device=Z.device)
+    _istft_out(Z, gain, nperseg, noverlap, window, fs, scaling, boundary, out)
+    return out
+
+
+_CX_ARGS = "int nperseg, int noverlap, str window, float fs, int scaling, int detrend, " \
+           "int boundary, bool padded"
+_op(f"stft_complex(Tensor x, {_CX_ARGS}) -> Tensor", _stft_complex,
+    lambda x, nperseg, noverlap, window, fs, scaling, detrend, boundary, padded:
+    x.new_empty((x.shape[0], nperseg // 2 + 1,
+                 _cx_frames(x.shape[1], nperseg, noverlap, boundary, padded)),
+                dtype=torch.complex64))
+_op(f"stft_complex_out(Tensor x, {_CX_ARGS}, Tensor(a!) out) -> ()", _stft_complex_out,
+    lambda *a: None)
+_IS_ARGS = "int nperseg, int noverlap, str window, float fs, int scaling, bool boundary"
+_op(f"istft(Tensor Z, Tensor? gain, {_IS_ARGS}) -> Tensor", _istft,
+    lambda Z, gain, nperseg, noverlap, window, fs, scaling, boundary:
+    Z.new_empty((Z.shape[0], _istft_len(Z.shape[2], nperseg, noverlap, boundary)),
+                dtype=torch.float32))
+_op(f"istft_out(Tensor Z, Tensor? gain, {_IS_ARGS}, Tensor(a!) out) -> ()", _istft_out,
+    lambda *a: None)
+
+
 # ---------------------------------------------------------------- cross spectrum
 def _csd(x, y, nperseg, noverlap, window, fs, scaling, detrend, mode):
     from . import cross

@@ -1,0 +1,86 @@
+"""numpy-in / numpy-out ``stft`` and ``istft`` with scipy.signal's signatures.
+
+Like the other compat entries (``pipeline_data.specgr``, ``cross.cross_spectrogram``) these
+upload, run the tensor path (``specenh.stft.stft`` / ``specenh.stft.istft``: the HIP kernels
+of csrc/stft_complex.hip through ``torch.ops.specenh``) and return float64 / complex128
+arrays of scipy's shapes. There is no CPU fallback.
+
+Differences from scipy, each one an exception rather than another result:
+``nfft != nperseg``, two-sided spectra, axes other than the defaults, and the ``'even'``,
+``'odd'`` and ``'constant'`` boundaries raise ``NotImplementedError``; ``nperseg`` must be a
+power of two in [64, 4096]; a signal shorter than ``nperseg`` raises ``ValueError``
+(scipy shrinks ``nperseg`` with a warning).
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import stft as _stft
+
+
+def _upload(t: torch.Tensor) -> torch.Tensor:
+    """To the current ROCm device. Without one the host tensor goes on: the tensor path
+    validates the arguments first and then refuses it (no CPU fallback)."""
+    return t.cuda() if torch.cuda.is_available() else t
+
+
+def _leading(a: np.ndarray, keep: int):
+    """Flatten the leading (batch) axes: returns (array [B, ...], leading shape)."""
+    lead = a.shape[:a.ndim - keep]
+    return a.reshape((-1,) + a.shape[a.ndim - keep:]), lead
+
+
+def stft(x, fs=1.0, window="hann", nperseg=256, noverlap=None, nfft=None, detrend=False,
+         return_onesided=True, boundary="zeros", padded=True, axis=-1, scaling="spectrum"):
+    """``scipy.signal.stft``: returns ``(f, t, Zxx)``, ``Zxx`` complex128 ``[..., F, T]``."""
+    if nfft is not None and int(nfft) != int(nperseg):
+        raise NotImplementedError("nfft != nperseg is not supported on the GPU path")
+    if not return_onesided:
+        raise NotImplementedError("two-sided spectra are not supported on the GPU path")
+    x = np.asarray(x)
+    if np.iscomplexobj(x):
+        raise NotImplementedError("complex input is not supported on the GPU path")
+    if x.ndim == 0:
+        raise ValueError("x must be at least 1-D")
+    if axis not in (-1, x.ndim - 1):
+        raise NotImplementedError("only axis=-1 is supported on the GPU path")
+    xb, lead = _leading(np.array(x, dtype=np.float32, order="C"), 1)
+    xt = torch.from_numpy(xb)
+    f, t, Z = _stft.stft(_upload(xt), fs=fs, window=window, nperseg=nperseg,
+                         noverlap=noverlap, detrend=detrend, boundary=boundary, padded=padded,
+                         scaling=scaling)
+    Z = Z.cpu().numpy().astype(np.complex128)
+    return f, t, Z.reshape(lead + Z.shape[1:])
+
+
+def istft(Zxx, fs=1.0, window="hann", nperseg=None, noverlap=None, nfft=None,
+          input_onesided=True, boundary=True, time_axis=-1, freq_axis=-2, scaling="spectrum",
+          gain=None):
+    """``scipy.signal.istft``: returns ``(t, x)``, ``x`` float64 ``[..., n]``. ``gain`` (not in
+    scipy): an optional real mask ``[..., F, T]`` or ``[..., F-1, T]`` multiplied into ``Zxx``
+    on the device while the bins are loaded. ``t`` has one entry per output sample (for a batched
+    ``Zxx`` scipy 1.15 sizes it by the leading axis instead)."""
+    if not input_onesided:
+        raise NotImplementedError("two-sided spectra are not supported on the GPU path")
+    Zxx = np.asarray(Zxx)
+    if Zxx.ndim < 2:
+        raise ValueError("Input stft must be at least 2d!")
+    if time_axis not in (-1, Zxx.ndim - 1) or freq_axis not in (-2, Zxx.ndim - 2):
+        raise NotImplementedError("only time_axis=-1, freq_axis=-2 are supported on the GPU path")
+    if nfft is not None and int(nfft) != 2 * (Zxx.shape[-2] - 1):
+        raise NotImplementedError("nfft != nperseg is not supported on the GPU path")
+    Zb, lead = _leading(np.array(Zxx, dtype=np.complex64, order="C"), 2)
+    g = None
+    if gain is not None:
+        g = np.asarray(gain)
+        if g.ndim != Zxx.ndim or g.shape[:-2] != Zxx.shape[:-2]:
+            raise ValueError(f"gain must be {Zxx.shape[:-2] + ('F or F-1', Zxx.shape[-1])}, got "
+                             f"{g.shape}")
+        g = torch.from_numpy(np.array(g, dtype=np.float32, order="C").reshape(
+            (-1,) + g.shape[-2:]))
+    t, x = _stft.istft(_upload(torch.from_numpy(Zb)), fs=fs, window=window,
+                       nperseg=nperseg, noverlap=noverlap, boundary=boundary, scaling=scaling,
+                       gain=g)
+    x = x.cpu().numpy().astype(np.float64)
+    return t, x.reshape(lead + x.shape[1:])

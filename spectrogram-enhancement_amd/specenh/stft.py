@@ -228,3 +228,143 @@ def stft_psd(x: torch.Tensor, nperseg: int, noverlap: int, window="hann", fs: fl
     ops.stft_psd_out(x, nperseg, noverlap, window_key(window, nperseg), float(fs),
                      _norm_scaling(scaling), _norm_detrend(detrend), float(eps), flags, out)
     return out[0] if squeeze else out
+
+
+# ------------------------------------------------------------------ complex STFT / inverse
+def _norm_boundary(boundary) -> int:
+    if boundary is None:
+        return _lib.BOUNDARY_NONE
+    if boundary == "zeros":
+        return _lib.BOUNDARY_ZEROS
+    if boundary in ("even", "odd", "constant"):
+        raise NotImplementedError(f"boundary={boundary!r} is not supported on the GPU path "
+                                  "(None or 'zeros')")
+    raise ValueError(f"Unknown boundary option '{boundary}', must be one of: "
+                     "['even', 'odd', 'constant', 'zeros', None]")
+
+
+def _norm_stft_scaling(scaling) -> int:
+    """scipy.signal.stft / istft name the two scalings 'spectrum' and 'psd'."""
+    if scaling == "spectrum":
+        return _lib.SCALING["spectrum"]
+    if scaling == "psd":
+        return _lib.SCALING["density"]
+    raise ValueError(f"Parameter scaling={scaling!r} not in ['spectrum', 'psd']!")
+
+
+def _check_nperseg(nperseg: int, noverlap) -> tuple:
+    nperseg = int(nperseg)
+    if nperseg < 1:
+        raise ValueError("nperseg must be a positive integer")
+    noverlap = nperseg // 2 if noverlap is None else int(noverlap)
+    if noverlap >= nperseg:
+        raise ValueError("noverlap must be less than nperseg.")
+    if noverlap < 0:
+        raise ValueError("noverlap must be a nonnegative integer")
+    if nperseg < 64 or nperseg > 4096 or nperseg & (nperseg - 1):
+        raise NotImplementedError("nperseg must be a power of two in [64, 4096] on the GPU path")
+    return nperseg, noverlap
+
+
+def complex_frame_count(length: int, nperseg: int, noverlap: int, boundary="zeros",
+                        padded: bool = True) -> int:
+    """Frames of ``scipy.signal.stft`` (specenh_stft_complex_frames)."""
+    return int(_lib.check(_lib.lib().specenh_stft_complex_frames(
+        int(length), int(nperseg), int(noverlap), _norm_boundary(boundary), int(bool(padded))),
+        "stft_complex_frames"))
+
+
+def istft_length(frames: int, nperseg: int, noverlap: int, boundary: bool = True) -> int:
+    """Output samples of ``scipy.signal.istft`` (specenh_istft_length)."""
+    return int(_lib.check(_lib.lib().specenh_istft_length(
+        int(frames), int(nperseg), int(noverlap), int(bool(boundary))), "istft_length"))
+
+
+def stft_times(length: int, nperseg: int, noverlap: int, fs: float, boundary="zeros",
+               padded: bool = True) -> np.ndarray:
+    """scipy.signal.stft's segment times (_spectral_helper), bit-identical (host, fp64)."""
+    hop = nperseg - noverlap
+    ext = length + (2 * (nperseg // 2) if boundary is not None else 0)
+    if padded:
+        ext += (-(ext - nperseg) % hop) % nperseg
+    time = np.arange(nperseg / 2, ext - nperseg / 2 + 1, nperseg - noverlap) / float(fs)
+    if boundary is not None:
+        time -= (nperseg / 2) / fs
+    return time
+
+
+def stft(x: torch.Tensor, fs: float = 1.0, window="hann", nperseg: int = 256, noverlap=None,
+         detrend=False, boundary="zeros", padded: bool = True, scaling="spectrum"):
+    """``scipy.signal.stft`` on a ROCm device: ``x[B, L]`` (or ``[L]``) fp32 ->
+    ``(f, t, Zxx)`` with ``Zxx[B, F, T]`` complex64 (``torch.ops.specenh.stft_complex``,
+    csrc/stft_complex.hip); ``f`` and ``t`` are scipy's float64 grids (host).
+
+    ``boundary`` is ``'zeros'`` or ``None``; the zero extension and the padding are applied
+    inside the kernel. A signal shorter than ``nperseg`` raises ``ValueError`` (scipy shrinks
+    ``nperseg`` with a warning instead).
+    """
+    from .ops import ops, window_key
+    nperseg, noverlap = _check_nperseg(nperseg, noverlap)
+    b = _norm_boundary(boundary)
+    sc, dt = _norm_stft_scaling(scaling), _norm_detrend(detrend)
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("x must be a torch.Tensor")
+    if x.dim() not in (1, 2):
+        raise ValueError("x must be [batch, length]")
+    L = x.shape[-1]
+    if L < nperseg:
+        raise ValueError(f"signal of {L} samples is shorter than nperseg = {nperseg}")
+    squeeze = x.dim() == 1
+    x = _check_input(x)
+    if x.dtype != torch.float32:
+        x = x.float()
+    Z = ops.stft_complex(x, nperseg, noverlap, window_key(window, nperseg), float(fs), sc, dt, b,
+                         bool(padded))
+    f = frequencies(nperseg, fs)
+    t = stft_times(L, nperseg, noverlap, fs, boundary, padded)
+    return f, t, (Z[0] if squeeze else Z)
+
+
+def istft(Zxx: torch.Tensor, fs: float = 1.0, window="hann", nperseg=None, noverlap=None,
+          boundary: bool = True, scaling="spectrum", gain: torch.Tensor | None = None):
+    """``scipy.signal.istft`` on a ROCm device: ``Zxx[B, F, T]`` (or ``[F, T]``) complex64 ->
+    ``(t, x)`` with ``x[B, n]`` fp32 (``torch.ops.specenh.istft``), deterministic overlap-add.
+
+    ``gain``: optional real fp32 mask ``[B, F, T]`` or ``[B, F-1, T]`` (the drop-Nyquist shape
+    of the denoisers; the Nyquist bin then gets gain 0) multiplied into ``Zxx`` while the
+    bins are loaded: ``istft(Zxx, gain=g)`` is ``istft(Zxx * g)`` without the masked copy.
+    """
+    from .ops import ops, window_key
+    if not isinstance(Zxx, torch.Tensor):
+        raise TypeError("Zxx must be a torch.Tensor")
+    if Zxx.dim() not in (2, 3):
+        raise ValueError("Input stft must be at least 2d!")
+    squeeze = Zxx.dim() == 2
+    if squeeze:
+        Zxx = Zxx.unsqueeze(0)
+        if gain is not None and gain.dim() == 2:
+            gain = gain.unsqueeze(0)
+    B, F, T = Zxx.shape
+    n_default = 2 * (F - 1)
+    if nperseg is None:
+        nperseg = n_default
+    if int(nperseg) != n_default:
+        raise ValueError(f"nperseg = {int(nperseg)} does not match the one-sided spectrogram: "
+                         f"2*(F - 1) = {n_default} (nfft != nperseg is not supported)")
+    nperseg, noverlap = _check_nperseg(nperseg, noverlap)
+    sc = _norm_stft_scaling(scaling)
+    if gain is not None:
+        if not isinstance(gain, torch.Tensor) or gain.dim() != 3 or gain.shape[0] != B or \
+                gain.shape[2] != T or gain.shape[1] not in (F, F - 1):
+            shape = tuple(gain.shape) if isinstance(gain, torch.Tensor) else type(gain)
+            raise ValueError(f"gain must be [{B}, {F}, {T}] or [{B}, {F - 1}, {T}], got {shape}")
+    if Zxx.device.type != "cuda":
+        raise RuntimeError("specenh.istft runs on the GPU only (no CPU fallback); "
+                           "move the spectrogram to a ROCm device first")
+    Zxx = Zxx.to(torch.complex64).resolve_conj().contiguous()
+    if gain is not None:
+        gain = gain.to(device=Zxx.device, dtype=torch.float32).contiguous()
+    x = ops.istft(Zxx, gain, nperseg, noverlap, window_key(window, nperseg), float(fs), sc,
+                  bool(boundary))
+    t = np.arange(x.shape[1]) / float(fs)
+    return t, (x[0] if squeeze else x)
