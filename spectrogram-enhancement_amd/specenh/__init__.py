@@ -7,6 +7,8 @@ Reference-compatible entry points (same names/arguments as the reference):
   specenh.keras         : layers / Model / compile / fit / predict / save / load_model
 scipy-compatible return path (complex STFT, gain mask, inverse STFT):
   specenh.signal        : stft, istft (numpy); specenh.stft.stft / istft (device tensors)
+scipy-compatible time-averaged spectra (Welch PSD, CSD, coherence, coherogram):
+  specenh.signal        : welch, csd, coherence (numpy); specenh.spectral (device tensors)
 Device fast paths: specgr_batch, denoise_batch, cross_spectrogram_batch, and
 specenh.autograd (differentiable Conv2D / Conv2DTranspose / MaxPooling2D / BCE).
 Every one of them reaches the HIP kernels through the ``torch.ops.specenh`` operators

@@ -190,6 +190,19 @@ SIGNATURES_STFT_COMPLEX = {
                                  _c.c_void_p]),
 }
 
+# time-averaged spectra (Welch / CSD / coherence); must match include/specenh_spectral.h
+SPECTRAL_CHUNK = 32  # SPECENH_SPECTRAL_CHUNK: frames summed in fp32 before fp64 takes over
+SPECTRAL_PXX, SPECTRAL_PYY, SPECTRAL_PXY, SPECTRAL_COH = 1, 2, 4, 8  # operator output mask
+SIGNATURES_SPECTRAL = {
+    "specenh_spectral_groups": (_c.c_longlong, [_c.c_longlong, _c.c_longlong]),
+    "specenh_spectral_workspace_bytes": (_c.c_size_t, [_c.c_void_p, _c.c_longlong,
+                                                       _c.c_longlong, _c.c_longlong]),
+    "specenh_spectral_mean": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_longlong,
+                                         _c.c_longlong, _c.c_longlong, _c.c_longlong,
+                                         _c.c_longlong, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                         _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+}
+
 
 def lib():
     """Load (once) and return the ctypes handle; raise ExtensionNotLoaded on failure."""
@@ -208,7 +221,8 @@ def lib():
         except OSError as e:
             raise ExtensionNotLoaded(f"failed to load {LIB_PATH}: {e}") from e
         dev_build = bool(os.environ.get("SPECENH_LIB"))
-        for name, (res, args) in {**SIGNATURES, **SIGNATURES_STFT_COMPLEX}.items():
+        for name, (res, args) in {**SIGNATURES, **SIGNATURES_STFT_COMPLEX,
+                                  **SIGNATURES_SPECTRAL}.items():
             if dev_build and not hasattr(h, name):
                 continue  # an older revision's build for an A/B run (tools/build_rev_lib.sh)
             fn = getattr(h, name)

@@ -258,6 +258,103 @@ _op("csd(Tensor x, Tensor y, int nperseg, int noverlap, str window, float fs, in
     "int detrend, int mode) -> Tensor", _csd, _csd_fake)
 
 
+# ---------------------------------------------------------------- averaged spectra
+_SP_DTYPES = (torch.float32, torch.float32, torch.complex64, torch.float32)
+
+
+def _sp_groups(T, navg):
+    return 1 if navg <= 0 else T // navg
+
+
+def _sp_shape(x, nperseg, noverlap, navg):
+    T = (x.shape[1] - nperseg) // (nperseg - noverlap) + 1
+    return x.shape[0], nperseg // 2 + 1, _sp_groups(T, navg)
+
+
+def _spectral_mean_out(x, y, nperseg, noverlap, window, fs, scaling, detrend, navg, pxx, pyy, pxy,
+                       coh, workspace):
+    from . import stft
+    for name, v in (("x", x), ("y", y)):
+        if v is not None and (v.dim() != 2 or v.stride(1) != 1 or v.dtype != torch.float32):
+            raise ValueError(f"{name} must be float32 [batch, length] with unit stride along "
+                             "length")
+    if y is not None and (y.shape != x.shape or y.device != x.device):
+        raise ValueError("x and y must have the same shape and device")
+    if noverlap >= nperseg:
+        raise ValueError("noverlap must be less than nperseg.")
+    B, L = x.shape
+    if L < nperseg:
+        raise ValueError("signal shorter than nperseg")
+    T = (L - nperseg) // (nperseg - noverlap) + 1
+    if navg > T:
+        raise ValueError(f"navg = {navg} exceeds the number of frames ({T})")
+    outs = (pxx, pyy, pxy, coh)
+    if all(o is None for o in outs):
+        raise ValueError("no output requested")
+    if y is None and any(o is not None for o in outs[1:]):
+        raise ValueError("pyy, pxy and coh need a second signal y")
+    shape = _sp_shape(x, nperseg, noverlap, navg)
+    for o, dt in zip(outs, _SP_DTYPES):
+        if o is not None and (tuple(o.shape) != shape or o.dtype != dt or not o.is_contiguous()
+                              or o.device != x.device):
+            raise ValueError(f"outputs must be contiguous {shape} on x's device (pxx, pyy, coh "
+                             "float32, pxy complex64)")
+    plan = stft.get_plan_key(x.device, nperseg, noverlap, window, fs, scaling, detrend, 0.0)
+    L_ = _lib.lib()
+    need = int(L_.specenh_spectral_workspace_bytes(plan.handle, B, L, navg))
+    if need and (workspace is None or workspace.device != x.device
+                 or not workspace.is_contiguous()
+                 or workspace.numel() * workspace.element_size() < need
+                 or workspace.data_ptr() % 16):
+        raise ValueError(f"workspace must be a contiguous, 16-byte aligned buffer of at least "
+                         f"{need} bytes on x's device")
+    _lib.check(L_.specenh_spectral_mean(
+        plan.handle, _vp(x), _vp(y), B, L, x.stride(0) if B > 1 else L,
+        (y.stride(0) if B > 1 else L) if y is not None else 0, int(navg), _vp(pxx), _vp(pyy),
+        _vp(pxy), _vp(coh), _vp(workspace if need else None), _st(x)), "spectral_mean")
+
+
+def spectral_workspace(x, nperseg, noverlap, window, fs, scaling, detrend, navg):
+    """A workspace for ``spectral_mean_out`` on ``x[B, L]`` (uint8; one byte when none is
+    needed), from torch's caching allocator."""
+    from . import stft
+    plan = stft.get_plan_key(x.device, nperseg, noverlap, window, fs, scaling, detrend, 0.0)
+    need = int(_lib.lib().specenh_spectral_workspace_bytes(plan.handle, x.shape[0], x.shape[1],
+                                                           int(navg)))
+    return torch.empty(max(need, 1), dtype=torch.uint8, device=x.device)
+
+
+def _spectral_mean(x, y, nperseg, noverlap, window, fs, scaling, detrend, navg, outputs):
+    if noverlap >= nperseg:
+        raise ValueError("noverlap must be less than nperseg.")
+    if x.dim() != 2 or x.dtype != torch.float32 or x.shape[1] < nperseg:
+        raise ValueError("x must be float32 [batch, length] with length >= nperseg")
+    T = (x.shape[1] - nperseg) // (nperseg - noverlap) + 1
+    if navg > T:
+        raise ValueError(f"navg = {navg} exceeds the number of frames ({T})")
+    shape = _sp_shape(x, nperseg, noverlap, navg)
+    outs = [torch.empty(shape, dtype=dt, device=x.device) if outputs >> i & 1 else None
+            for i, dt in enumerate(_SP_DTYPES)]
+    ws = spectral_workspace(x, nperseg, noverlap, window, fs, scaling, detrend, navg)
+    _spectral_mean_out(x, y, nperseg, noverlap, window, fs, scaling, detrend, navg, *outs, ws)
+    return tuple(x.new_empty((0,), dtype=dt) if o is None else o
+                 for o, dt in zip(outs, _SP_DTYPES))
+
+
+def _spectral_mean_fake(x, y, nperseg, noverlap, window, fs, scaling, detrend, navg, outputs):
+    shape = _sp_shape(x, nperseg, noverlap, navg)
+    return tuple(x.new_empty(shape if outputs >> i & 1 else (0,), dtype=dt)
+                 for i, dt in enumerate(_SP_DTYPES))
+
+
+_SP_ARGS = "int nperseg, int noverlap, str window, float fs, int scaling, int detrend, int navg"
+_op(f"spectral_mean(Tensor x, Tensor? y, {_SP_ARGS}, int outputs) -> "
+    "(Tensor, Tensor, Tensor, Tensor)", _spectral_mean, _spectral_mean_fake)
+_op(f"spectral_mean_out(Tensor x, Tensor? y, {_SP_ARGS}, Tensor(a!)? pxx, Tensor(b!)? pyy, "
+    "Tensor(c!)? pxy, Tensor(d!)? coh, Tensor(e!)? workspace) -> ()", _spectral_mean_out,
+    lambda *a: None)
+
+
 # ---------------------------------------------------------------- SVD denoiser
 def _bstride(A):
     """Batch stride for the C-ABI: a batch of one may carry any stride (e.g. 0 from a numpy

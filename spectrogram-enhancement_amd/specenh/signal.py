@@ -1,9 +1,11 @@
-"""numpy-in / numpy-out ``stft`` and ``istft`` with scipy.signal's signatures.
+"""numpy-in / numpy-out ``stft``, ``istft``, ``welch``, ``csd`` and ``coherence`` with
+scipy.signal's signatures.
 
 Like the other compat entries (``pipeline_data.specgr``, ``cross.cross_spectrogram``) these
 upload, run the tensor path (``specenh.stft.stft`` / ``specenh.stft.istft``: the HIP kernels
 of csrc/stft_complex.hip through ``torch.ops.specenh``) and return float64 / complex128
-arrays of scipy's shapes. There is no CPU fallback.
+arrays of scipy's shapes. ``welch`` / ``csd`` / ``coherence`` run ``specenh.spectral`` (one
+fused launch of csrc/spectral_mean.hip; ``average='mean'`` only). There is no CPU fallback.
 
 Differences from scipy, each one an exception rather than another result:
 ``nfft != nperseg``, two-sided spectra, axes other than the defaults, and the ``'even'``,
@@ -16,6 +18,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from . import spectral as _spectral
 from . import stft as _stft
 
 
@@ -84,3 +87,56 @@ def istft(Zxx, fs=1.0, window="hann", nperseg=None, noverlap=None, nfft=None,
                        gain=g)
     x = x.cpu().numpy().astype(np.float64)
     return t, x.reshape(lead + x.shape[1:])
+
+
+def _averaged(which, x, y, fs, window, nperseg, noverlap, nfft, detrend, return_onesided,
+              scaling, axis, average):
+    nperseg = 256 if nperseg is None else int(nperseg)
+    if nfft is not None and int(nfft) != nperseg:
+        raise NotImplementedError("nfft != nperseg is not supported on the GPU path")
+    if not return_onesided:
+        raise NotImplementedError("two-sided spectra are not supported on the GPU path")
+    if average != "mean":
+        if average == "median":
+            raise NotImplementedError("average='median' is not supported on the GPU path")
+        raise ValueError(f"average must be 'median' or 'mean', got {average}")
+    arrs = [np.asarray(v) for v in (x, y) if v is not None]
+    for a in arrs:
+        if np.iscomplexobj(a):
+            raise NotImplementedError("complex input is not supported on the GPU path")
+        if a.ndim == 0:
+            raise ValueError("x must be at least 1-D")
+        if axis not in (-1, a.ndim - 1):
+            raise NotImplementedError("only axis=-1 is supported on the GPU path")
+    if len(arrs) == 2 and arrs[0].shape != arrs[1].shape:
+        raise ValueError("x and y must have the same shape (scipy would broadcast / zero-pad)")
+    lead = arrs[0].shape[:-1]
+    ts = [_upload(torch.from_numpy(_leading(np.array(a, dtype=np.float32, order="C"), 1)[0]))
+          for a in arrs]
+    f, _, est = _spectral.spectral_estimates(
+        ts[0], ts[1] if len(ts) == 2 else None, fs=fs, window=window, nperseg=nperseg,
+        noverlap=noverlap, detrend=detrend, scaling=scaling, want=(which,))
+    P = est[which][..., 0].cpu().numpy()
+    P = P.astype(np.complex128 if which == "pxy" else np.float64)
+    return f, P.reshape(lead + P.shape[1:])
+
+
+def welch(x, fs=1.0, window="hann", nperseg=None, noverlap=None, nfft=None, detrend="constant",
+          return_onesided=True, scaling="density", axis=-1, average="mean"):
+    """``scipy.signal.welch``: returns ``(f, Pxx)``, ``Pxx`` float64 ``[..., F]``."""
+    return _averaged("pxx", x, None, fs, window, nperseg, noverlap, nfft, detrend,
+                     return_onesided, scaling, axis, average)
+
+
+def csd(x, y, fs=1.0, window="hann", nperseg=None, noverlap=None, nfft=None, detrend="constant",
+        return_onesided=True, scaling="density", axis=-1, average="mean"):
+    """``scipy.signal.csd``: returns ``(f, Pxy)``, ``Pxy`` complex128 ``[..., F]``."""
+    return _averaged("pxy", x, y, fs, window, nperseg, noverlap, nfft, detrend, return_onesided,
+                     scaling, axis, average)
+
+
+def coherence(x, y, fs=1.0, window="hann", nperseg=None, noverlap=None, nfft=None,
+              detrend="constant", axis=-1):
+    """``scipy.signal.coherence``: returns ``(f, Cxy)``, ``Cxy`` float64 ``[..., F]``."""
+    return _averaged("coh", x, y, fs, window, nperseg, noverlap, nfft, detrend, True, "density",
+                     axis, "mean")
