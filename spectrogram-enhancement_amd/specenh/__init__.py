@@ -9,6 +9,9 @@ scipy-compatible return path (complex STFT, gain mask, inverse STFT):
   specenh.signal        : stft, istft (numpy); specenh.stft.stft / istft (device tensors)
 scipy-compatible time-averaged spectra (Welch PSD, CSD, coherence, coherogram):
   specenh.signal        : welch, csd, coherence (numpy); specenh.spectral (device tensors)
+cross-spectral matrix and coherence matrix of a channel array (every pair in one call):
+  specenh.signal.cross_spectral_matrix (numpy); specenh.spectral.cross_spectral_matrix,
+  coherence_matrix (device tensors)
 Device fast paths: specgr_batch, denoise_batch, cross_spectrogram_batch, and
 specenh.autograd (differentiable Conv2D / Conv2DTranspose / MaxPooling2D / BCE).
 Every one of them reaches the HIP kernels through the ``torch.ops.specenh`` operators

@@ -203,6 +203,22 @@ SIGNATURES_SPECTRAL = {
                                          _c.c_void_p, _c.c_void_p, _c.c_void_p]),
 }
 
+# cross-spectral matrix of a channel array; must match include/specenh_csm.h
+CSM_MAX_CHANNELS = 64  # SPECENH_CSM_MAX_CHANNELS
+CSM_CSM, CSM_COH = 1, 2  # operator output mask
+# The tensor layer splits the batch so that one launch's workspace (the spectra of every
+# frame, 8 B F T C bytes a shot) stays under this many bytes; a single shot above it still
+# runs alone. Results do not depend on the split.
+CSM_WORKSPACE_CAP = 1 << 30
+SIGNATURES_CSM = {
+    "specenh_csm_workspace_bytes": (_c.c_size_t, [_c.c_void_p, _c.c_longlong, _c.c_longlong,
+                                                  _c.c_longlong, _c.c_longlong]),
+    "specenh_csm": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_longlong, _c.c_longlong,
+                               _c.c_longlong, _c.c_longlong, _c.c_longlong, _c.c_longlong,
+                               _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t,
+                               _c.c_void_p]),
+}
+
 
 def lib():
     """Load (once) and return the ctypes handle; raise ExtensionNotLoaded on failure."""
@@ -222,7 +238,7 @@ def lib():
             raise ExtensionNotLoaded(f"failed to load {LIB_PATH}: {e}") from e
         dev_build = bool(os.environ.get("SPECENH_LIB"))
         for name, (res, args) in {**SIGNATURES, **SIGNATURES_STFT_COMPLEX,
-                                  **SIGNATURES_SPECTRAL}.items():
+                                  **SIGNATURES_SPECTRAL, **SIGNATURES_CSM}.items():
             if dev_build and not hasattr(h, name):
                 continue  # an older revision's build for an A/B run (tools/build_rev_lib.sh)
             fn = getattr(h, name)

@@ -355,6 +355,109 @@ _op(f"spectral_mean_out(Tensor x, Tensor? y, {_SP_ARGS}, Tensor(a!)? pxx, Tensor
     lambda *a: None)
 
 
+# ---------------------------------------------------------------- cross-spectral matrix
+_CSM_DTYPES = (torch.complex64, torch.float32)
+
+
+def _csm_shape(x, nperseg, noverlap, navg):
+    T = (x.shape[2] - nperseg) // (nperseg - noverlap) + 1
+    C = x.shape[1]
+    return x.shape[0], nperseg // 2 + 1, _sp_groups(T, navg), C, C
+
+
+def _csm_check(x, nperseg, noverlap, navg):
+    if x.dim() != 3 or x.dtype != torch.float32 or x.stride(2) != 1:
+        raise ValueError("x must be float32 [batch, channels, length] with unit stride along "
+                         "length")
+    if noverlap >= nperseg:
+        raise ValueError("noverlap must be less than nperseg.")
+    B, C, L = x.shape
+    if not 2 <= C <= _lib.CSM_MAX_CHANNELS:
+        raise ValueError(f"channels must be in [2, {_lib.CSM_MAX_CHANNELS}], got {C}")
+    if L < nperseg:
+        raise ValueError("signal shorter than nperseg")
+    T = (L - nperseg) // (nperseg - noverlap) + 1
+    if navg > T:
+        raise ValueError(f"navg = {navg} exceeds the number of frames ({T})")
+
+
+def _csm_strides(x):
+    """(channel_stride, batch_stride) of x[B, C, L]; the stride of a one-element axis is free."""
+    B, C, L = x.shape
+    cs = x.stride(1) if C > 1 else L
+    bs = x.stride(0) if B > 1 else C * cs
+    if cs < L or bs < C * cs:
+        raise ValueError("x must not overlap itself: channel stride >= length and batch stride "
+                         ">= channels * channel stride")
+    return cs, bs
+
+
+def _csm_need(x, nperseg, noverlap, window, fs, scaling, detrend, navg):
+    from . import stft
+    plan = stft.get_plan_key(x.device, nperseg, noverlap, window, fs, scaling, detrend, 0.0)
+    B, C, L = x.shape
+    need = int(_lib.lib().specenh_csm_workspace_bytes(plan.handle, B, C, L, int(navg)))
+    if need == 0 and B > 0:
+        _lib.check(_lib.SPECENH_EINVAL, "csm_workspace_bytes")
+    return plan, need
+
+
+def csm_workspace(x, nperseg, noverlap, window, fs, scaling, detrend, navg):
+    """A workspace for ``csm_out`` on ``x[B, C, L]`` (uint8, from torch's caching allocator):
+    the spectra of every frame that enters a group, ``8 B F T C`` bytes."""
+    _csm_check(x, nperseg, noverlap, navg)
+    _, need = _csm_need(x, nperseg, noverlap, window, fs, scaling, detrend, navg)
+    return torch.empty(max(need, 1), dtype=torch.uint8, device=x.device)
+
+
+def _csm_out(x, nperseg, noverlap, window, fs, scaling, detrend, navg, csm, coh, workspace):
+    _csm_check(x, nperseg, noverlap, navg)
+    cs, bs = _csm_strides(x)
+    outs = (csm, coh)
+    if all(o is None for o in outs):
+        raise ValueError("no output requested")
+    shape = _csm_shape(x, nperseg, noverlap, navg)
+    for o, dt in zip(outs, _CSM_DTYPES):
+        if o is not None and (tuple(o.shape) != shape or o.dtype != dt or not o.is_contiguous()
+                              or o.device != x.device):
+            raise ValueError(f"outputs must be contiguous {shape} on x's device (csm complex64, "
+                             "coh float32)")
+    plan, need = _csm_need(x, nperseg, noverlap, window, fs, scaling, detrend, navg)
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=x.device)
+    if (workspace.device != x.device or not workspace.is_contiguous()
+            or workspace.numel() * workspace.element_size() < need or workspace.data_ptr() % 16):
+        raise ValueError(f"workspace must be a contiguous, 16-byte aligned buffer of at least "
+                         f"{need} bytes on x's device")
+    B, C, L = x.shape
+    _lib.check(_lib.lib().specenh_csm(
+        plan.handle, _vp(x), B, C, L, cs, bs, int(navg), _vp(csm), _vp(coh), _vp(workspace),
+        workspace.numel() * workspace.element_size(), _st(x)), "csm")
+
+
+def _csm(x, nperseg, noverlap, window, fs, scaling, detrend, navg, outputs):
+    _csm_check(x, nperseg, noverlap, navg)
+    if not outputs & 3:
+        raise ValueError("no output requested")
+    shape = _csm_shape(x, nperseg, noverlap, navg)
+    outs = [torch.empty(shape, dtype=dt, device=x.device) if outputs >> i & 1 else None
+            for i, dt in enumerate(_CSM_DTYPES)]
+    _csm_out(x, nperseg, noverlap, window, fs, scaling, detrend, navg, *outs, None)
+    return tuple(x.new_empty((0,), dtype=dt) if o is None else o
+                 for o, dt in zip(outs, _CSM_DTYPES))
+
+
+def _csm_fake(x, nperseg, noverlap, window, fs, scaling, detrend, navg, outputs):
+    shape = _csm_shape(x, nperseg, noverlap, navg)
+    return tuple(x.new_empty(shape if outputs >> i & 1 else (0,), dtype=dt)
+                 for i, dt in enumerate(_CSM_DTYPES))
+
+
+_op(f"csm(Tensor x, {_SP_ARGS}, int outputs) -> (Tensor, Tensor)", _csm, _csm_fake)
+_op(f"csm_out(Tensor x, {_SP_ARGS}, Tensor(a!)? csm, Tensor(b!)? coh, Tensor(c!)? workspace) "
+    "-> ()", _csm_out, lambda *a: None)
+
+
 # ---------------------------------------------------------------- SVD denoiser
 def _bstride(A):
     """Batch stride for the C-ABI: a batch of one may carry any stride (e.g. 0 from a numpy

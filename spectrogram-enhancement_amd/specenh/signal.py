@@ -5,7 +5,9 @@ Like the other compat entries (``pipeline_data.specgr``, ``cross.cross_spectrogr
 upload, run the tensor path (``specenh.stft.stft`` / ``specenh.stft.istft``: the HIP kernels
 of csrc/stft_complex.hip through ``torch.ops.specenh``) and return float64 / complex128
 arrays of scipy's shapes. ``welch`` / ``csd`` / ``coherence`` run ``specenh.spectral`` (one
-fused launch of csrc/spectral_mean.hip; ``average='mean'`` only). There is no CPU fallback.
+fused launch of csrc/spectral_mean.hip; ``average='mean'`` only). ``cross_spectral_matrix``
+(not in scipy) gives ``csd`` / ``coherence`` of every channel pair of an array in one call
+(csrc/spectral_matrix.hip). There is no CPU fallback.
 
 Differences from scipy, each one an exception rather than another result:
 ``nfft != nperseg``, two-sided spectra, axes other than the defaults, and the ``'even'``,
@@ -140,3 +142,38 @@ def coherence(x, y, fs=1.0, window="hann", nperseg=None, noverlap=None, nfft=Non
     """``scipy.signal.coherence``: returns ``(f, Cxy)``, ``Cxy`` float64 ``[..., F]``."""
     return _averaged("coh", x, y, fs, window, nperseg, noverlap, nfft, detrend, True, "density",
                      axis, "mean")
+
+
+def cross_spectral_matrix(x, fs=1.0, window="hann", nperseg=None, noverlap=None, nfft=None,
+                          detrend="constant", return_onesided=True, scaling="density", axis=-1,
+                          average="mean", navg=None, want=("csm", "coh")):
+    """The cross-spectral matrix of a channel array ``x[..., C, L]`` (not in scipy: one call of
+    ``specenh.spectral.cross_spectral_matrix`` instead of ``scipy.signal.csd`` per channel
+    pair). Returns ``(f, t_groups, est)``: ``est["csm"]`` complex128 and ``est["coh"]``
+    float64, ``[..., F, G, C, C]``; the leading axes are flattened into the batch and
+    restored."""
+    nperseg = 256 if nperseg is None else int(nperseg)
+    if nfft is not None and int(nfft) != nperseg:
+        raise NotImplementedError("nfft != nperseg is not supported on the GPU path")
+    if not return_onesided:
+        raise NotImplementedError("two-sided spectra are not supported on the GPU path")
+    if average != "mean":
+        if average == "median":
+            raise NotImplementedError("average='median' is not supported on the GPU path")
+        raise ValueError(f"average must be 'median' or 'mean', got {average}")
+    a = np.asarray(x)
+    if np.iscomplexobj(a):
+        raise NotImplementedError("complex input is not supported on the GPU path")
+    if a.ndim < 2:
+        raise ValueError("x must be at least 2-D: [..., channels, length]")
+    if axis not in (-1, a.ndim - 1):
+        raise NotImplementedError("only axis=-1 is supported on the GPU path")
+    xb, lead = _leading(np.array(a, dtype=np.float32, order="C"), 2)
+    f, t, est = _spectral.cross_spectral_matrix(
+        _upload(torch.from_numpy(xb)), fs=fs, window=window, nperseg=nperseg, noverlap=noverlap,
+        detrend=detrend, scaling=scaling, navg=navg, want=want)
+    out = {}
+    for name, v in est.items():
+        v = v.cpu().numpy().astype(np.complex128 if name == "csm" else np.float64)
+        out[name] = v.reshape(lead + v.shape[1:])
+    return f, t, out

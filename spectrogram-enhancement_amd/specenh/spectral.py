@@ -14,6 +14,11 @@ Differences from scipy, each an exception rather than another result: ``nperseg`
 power of two in [64, 4096]; a signal shorter than ``nperseg`` and ``x``, ``y`` of different
 shapes raise ``ValueError`` (scipy shrinks ``nperseg`` / zero-pads); ``average='median'``
 raises ``NotImplementedError``.
+
+Channel arrays: ``cross_spectral_matrix`` / ``coherence_matrix`` give the Hermitian matrix of
+all channel pairs ``[B, F, G, C, C]`` in one call (csrc/spectral_matrix.hip through
+``torch.ops.specenh.csm`` -> ``specenh_csm``): every frame is transformed once, then summed as
+a Gram product per frequency on the fp32 matrix cores.
 """
 from __future__ import annotations
 
@@ -134,3 +139,85 @@ def coherence(x: torch.Tensor, y: torch.Tensor, fs: float = 1.0, window="hann",
     f, _, est = spectral_estimates(x, y, fs, window, nperseg, noverlap, detrend, "density",
                                    "mean", None, ("coh",))
     return f, est["coh"][..., 0]
+
+
+# ---------------------------------------------------------------- channel arrays
+_CSM_BITS = {"csm": _lib.CSM_CSM, "coh": _lib.CSM_COH}
+# One launch's workspace stays under this many bytes (the batch is split into several
+# launches; a single shot above it still runs alone). Results do not depend on the split.
+CSM_WORKSPACE_CAP = _lib.CSM_WORKSPACE_CAP
+
+
+def _prep_array(x):
+    if x.dim() == 2:
+        x = x.unsqueeze(0)
+    if x.dtype != torch.float32:
+        x = x.float()
+    B, C, L = x.shape
+    cs = x.stride(1) if C > 1 else L
+    bs = x.stride(0) if B > 1 else C * cs
+    return x if x.stride(2) == 1 and cs >= L and bs >= C * cs else x.contiguous()
+
+
+def cross_spectral_matrix(x: torch.Tensor, fs: float = 1.0, window="hann", nperseg: int = 256,
+                          noverlap=None, detrend="constant", scaling="density", navg=None,
+                          want=("csm", "coh")):
+    """The cross-spectral matrix of a channel array ``x[B, C, L]`` on a ROCm device
+    (csrc/spectral_matrix.hip through ``torch.ops.specenh.csm``): every channel's frames are
+    transformed once, then summed as a Gram product per frequency on the matrix cores.
+
+    Returns ``(f, t_groups, est)``: ``est["csm"]`` complex64 ``[B, F, G, C, C]`` with
+    ``[..., i, j]`` what ``scipy.signal.csd(x_i, x_j, ..., average='mean')`` gives on group
+    ``g``'s slice (the groups of ``spectral_estimates``), Hermitian bit for bit with a real
+    diagonal (the Welch PSDs); ``est["coh"]`` float32 ``|S_ij|^2 / (S_ii S_jj)`` (0/0 is NaN).
+    ``2 <= C <= 64``. ``x[C, L]`` gives ``[F, G, C, C]``.
+    """
+    from .ops import ops, csm_workspace, window_key
+    nperseg, noverlap = _check_nperseg(nperseg, noverlap)
+    sc, dt = _norm_scaling(scaling), _norm_detrend(detrend)
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("x must be a torch.Tensor")
+    if x.dim() not in (2, 3):
+        raise ValueError("x must be [batch, channels, length] or [channels, length]")
+    squeeze = x.dim() == 2
+    want = tuple(want)
+    if not want or any(w not in _CSM_BITS for w in want):
+        raise ValueError(f"want must name some of {tuple(_CSM_BITS)}, got {want}")
+    C, L = x.shape[-2], x.shape[-1]
+    if not 2 <= C <= _lib.CSM_MAX_CHANNELS:
+        raise ValueError(f"channels must be in [2, {_lib.CSM_MAX_CHANNELS}], got {C} "
+                         "(one channel: welch)")
+    if L < nperseg:
+        raise ValueError(f"signal of {L} samples is shorter than nperseg = {nperseg}")
+    navg = int(navg or 0)
+    T = (L - nperseg) // (nperseg - noverlap) + 1
+    if navg > T:
+        raise ValueError(f"navg = {navg} exceeds the number of frames ({T})")
+    if x.device.type != "cuda":
+        raise RuntimeError("specenh.spectral runs on the GPU only (no CPU fallback); "
+                           "move the signals to a ROCm device first")
+    x = _prep_array(x)
+    B = x.shape[0]
+    G = 1 if navg <= 0 else T // navg
+    key = window_key(window, nperseg)
+    args = (nperseg, noverlap, key, float(fs), sc, dt, navg)
+    shape = (B, nperseg // 2 + 1, G, C, C)
+    outs = [torch.empty(shape, dtype=d, device=x.device) if w in want else None
+            for w, d in (("csm", torch.complex64), ("coh", torch.float32))]
+    per_shot = 8 * shape[1] * G * (navg if navg >= 1 else T) * C  # workspace bytes a shot
+    step = max(1, int(CSM_WORKSPACE_CAP) // per_shot)
+    ws = csm_workspace(x[:min(step, B)], *args) if B else None
+    for b0 in range(0, B, step):
+        b1 = min(B, b0 + step)
+        ops.csm_out(x[b0:b1], *args, *(None if o is None else o[b0:b1] for o in outs), ws)
+    est = {w: (o[0] if squeeze else o) for w, o in zip(("csm", "coh"), outs) if o is not None}
+    return frequencies(nperseg, fs), group_times(L, nperseg, noverlap, fs, navg), est
+
+
+def coherence_matrix(x: torch.Tensor, fs: float = 1.0, window="hann", nperseg: int = 256,
+                     noverlap=None, detrend="constant"):
+    """``scipy.signal.coherence`` of every channel pair of ``x[B, C, L]``:
+    ``(f, Cxy[B, F, C, C])`` float32 on the device (``[F, C, C]`` for ``x[C, L]``)."""
+    f, _, est = cross_spectral_matrix(x, fs, window, nperseg, noverlap, detrend, "density", None,
+                                      ("coh",))
+    return f, est["coh"][..., 0, :, :]
