@@ -88,7 +88,8 @@ def test_gpu_batched_pairs_and_amplitude(gpu_device, n, ov):
 @pytest.mark.parametrize("n,ov,win,det,sc", [(1024, 768, "hamm", "linear", "density"),
                                              (512, 256, "hann", "constant", "spectrum"),
                                              (256, 128, "blackman", False, "density"),
-                                             (64, 32, "hann", "linear", "density")])
+                                             (64, 32, "hann", "linear", "density"),
+                                             (128, 96, "hamm", "constant", "density")])
 def test_gpu_amplitude_team_schedule(gpu_device, n, ov, win, det, sc):
     """|Pxy| on the STFT team kernel (MODE 3) at many frames per pair, strided rows,
     against the fp64 oracle: every tile, the ragged last tile and the DC/Nyquist rows."""

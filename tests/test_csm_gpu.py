@@ -35,6 +35,9 @@ PARITY = [
     (33, 256, 128, "hamm", "constant", 0, "density"),  # C crosses the tile
     (64, 1024, 768, "hamm", "linear", 1, "density"),   # the maximum C, groups of one frame
     (5, 4096, 3072, "hann", False, 3, "density"),
+    (9, 128, 96, "hann", "linear", 0, "density"),      # 8 + 1 channels: a ragged second block
+    (5, 2048, 1536, "hann", "linear", 0, "density"),   # 4 slots: blocks of 4 + 1
+    (6, 2048, 1024, "hamm", False, 2, "spectrum"),     # 4 slots with frame groups
 ]
 LONG = [(3, 64, 48, "hann", "linear", 0, "density"),   # T = 4101: 129 chunks
         (3, 64, 48, "hann", "linear", 7, "density")]   # G = 585, 6 frames dropped

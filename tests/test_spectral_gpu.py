@@ -33,6 +33,10 @@ PARITY = [
     (512, 256, "hamm", "linear", 4, "density"),      # T = 17: G = 4, one frame dropped
     (1024, 768, "hamm", "linear", 1, "density"),     # T = 33 groups of one frame
     (4096, 3072, "hann", False, 3, "density"),       # T = 33: G = 11
+    (128, 96, "hamm", "linear", 0, "density"),       # T = 34: chunks of 32 + 2, the workspace path
+    (128, 64, "hann", "constant", 3, "spectrum"),    # T = 17: G = 5, two frames dropped
+    (2048, 1536, "hann", "linear", 0, "density"),    # T = 33: chunks 32 + 1; the 2048 kernels
+    (2048, 1024, "hamm", False, 2, "density"),       # T = 17: G = 8, one frame dropped
 ]
 LONG = [(64, 48, "hann", "linear", 0, "density"),    # T = 4101: 129 chunks
         (64, 48, "hann", "linear", 7, "density")]    # G = 585, 6 frames dropped

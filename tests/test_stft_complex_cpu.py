@@ -25,6 +25,10 @@ CASES = [
     (333, 64, 32, "hann"),
     (300, 64, 63, "hamm"),
     (640, 64, 0, "hamm"),
+    (9000, 128, 96, "hann"),
+    (12300, 512, 200, "hamm"),
+    (20000, 2048, 1536, "hann"),
+    (9010, 64, 48, "hamm"),
 ]
 MODES = [("zeros", True), (None, True), ("zeros", False), (None, False)]
 
@@ -77,6 +81,25 @@ def test_frames_lengths_and_grids_match_scipy(L, nperseg, noverlap, window):
                                         noverlap=noverlap, boundary=inv_boundary)
             n = lib.specenh_istft_length(T, nperseg, noverlap, int(inv_boundary))
             assert n == xi.shape[0] == stft.istft_length(T, nperseg, noverlap, inv_boundary)
+
+
+@pytest.mark.parametrize("case,frames,spans", [
+    ((9000, 128, 96, "hann"), (283, 279, 282), 3),
+    ((12300, 512, 200, "hamm"), (41, 39, 40), 4),
+    ((20000, 2048, 1536, "hann"), (41, 37, 40), 5),
+    ((9010, 64, 48, "hamm"), (565, 561, 564), 3),
+])
+def test_odd_size_cases_have_the_frames_and_spans_they_are_chosen_for(case, frames, spans):
+    """The frame counts (boundary='zeros' padded, boundary=None padded, boundary='zeros'
+    unpadded) and the inverse's workgroup count (4096 output samples each) that the comments
+    of tests/test_stft_complex_gpu.py state: an odd and an even T per size, more than one
+    span."""
+    from specenh import stft
+
+    L, n, nov, w = case
+    got = tuple(stft.complex_frame_count(L, n, nov, b, p) for b, p in MODES[:3])
+    assert got == frames
+    assert -(-stft.istft_length(frames[0], n, nov, True) // 4096) == spans
 
 
 def test_frame_count_errors():

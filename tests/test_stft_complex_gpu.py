@@ -2,7 +2,8 @@
 istft called in fp64 on the fp32 samples widened.
 
 Bounds: 1e-5 normwise (max|got - ref| / max|ref| per spectrogram or signal), the project's
-contract for fp32 spectra. Every output buffer is NaN-filled before the
+contract for fp32 spectra, and the same 1e-5 per frame pair and per output
+sample on shots whose level changes by four decades. Every output buffer is NaN-filled before the
 launch, so an element the kernel does not write fails the comparison. Each test prints its
 measured maximum (pytest -s); DESIGN.md records them.
 """
@@ -12,6 +13,8 @@ import numpy as np
 import pytest
 import scipy.signal
 import torch
+
+import stft_local as sl
 
 pytestmark = pytest.mark.gpu
 
@@ -27,7 +30,13 @@ BASE = [
     (333, 64, 32, "hann"),        # T = 12: shorter than one tile, tail mostly zero-extension
     (300, 64, 63, "hamm"),        # hop 1: 64 frames under every sample
     (640, 64, 0, "hamm"),         # hop = nperseg: no overlap at all
+    # odd log2(nperseg): the radix-2 pass, then radix-4 from Ns = 2, forward and inverse
+    (9000, 128, 96, "hann"),      # T = 283 (odd): 17 tiles of 16 + 11; inverse in 3 spans
+    (12300, 512, 200, "hamm"),    # T = 41 (odd): 5 tiles of 8 + 1; hop 312; 4 spans
+    (20000, 2048, 1536, "hann"),  # T = 41 (odd): 10 tiles of 4 + 1; 5 spans
+    (9010, 64, 48, "hamm"),       # T = 565 (odd): nperseg 64 across span edges, 3 spans
 ]
+ODD = BASE[8:11]  # nperseg 128, 512, 2048
 # (case, boundary, padded, detrend, scaling)
 CONFIGS = [(c, "zeros", True, False, "spectrum") for c in BASE]
 CONFIGS += [(c, None, True, False, "spectrum") for c in BASE[:3]]
@@ -35,6 +44,10 @@ CONFIGS += [(c, "zeros", False, False, "spectrum") for c in BASE[:3]]
 CONFIGS += [(BASE[1], "zeros", True, "constant", "spectrum"),
             (BASE[1], "zeros", True, "linear", "spectrum"),
             (BASE[0], "zeros", True, False, "psd")]
+CONFIGS += [(c, None, True, False, "spectrum") for c in ODD[:2]]     # T = 279, 39
+CONFIGS += [(c, "zeros", False, False, "spectrum") for c in ODD[:2]]  # T = 282, 40: even
+CONFIGS += [(ODD[2], "zeros", True, "linear", "spectrum"),
+            (ODD[2], "zeros", True, False, "psd")]
 
 
 def _id(cfg):
@@ -137,6 +150,42 @@ def test_inverse_matches_scipy(gpu_device, cfg):
     got = inverse(to_dev(Z32, gpu_device), cfg)
     assert got.dtype == torch.float32 and got.shape[1] == xi.shape[-1]
     check("inverse " + _id(cfg), got.cpu().numpy().astype(np.float64), xi)
+
+
+# Localised error. normwise() divides by the loudest value of a whole shot, so on a shot whose
+# level changes it lets any error through at the quiet end. The shots of tests/stft_local.py
+# fall (or, reversed, rise) by four decades, and the error is measured where the algorithm
+# bounds it: per frame against the louder frame of its pair (2q, 2q + 1), per output sample
+# against the loudest sample within nperseg + hop. tests/test_stft_complex_local_cpu.py shows a
+# plain emulation of the algorithm below 3e-7 under both metrics on the same inputs.
+@pytest.mark.parametrize("reverse", [False, True], ids=["falling", "rising"])
+@pytest.mark.parametrize("case", sl.LOCAL, ids=sl.LOCAL_IDS)
+def test_forward_error_per_frame_pair(gpu_device, case, reverse):
+    Z, Z32, xi = sl.reference(case, reverse)
+    cfg = (case, "zeros", True, False, "spectrum")
+    got = forward(to_dev(sl.shots(case, reverse), gpu_device), cfg)
+    assert got.dtype == torch.complex64 and tuple(got.shape) == Z.shape
+    e = sl.frame_error(got.cpu().numpy(), Z)
+    b, t = np.unravel_index(np.nanargmax(e) if not np.isnan(e).all() else 0, e.shape)
+    print(f"[stft_complex] forward per pair {_id(cfg)} {'rising' if reverse else 'falling'}: "
+          f"max err {e.max():.3e} (shot {b}, frame {t} of {e.shape[1]}); normwise "
+          f"{normwise(got.cpu().numpy().astype(np.complex128), Z):.3e}")
+    assert not np.isnan(e).any() and e.max() <= TOL, f"{e.max():.3e} > {TOL} at frame {t}"
+
+
+@pytest.mark.parametrize("reverse", [False, True], ids=["falling", "rising"])
+@pytest.mark.parametrize("case", sl.LOCAL, ids=sl.LOCAL_IDS)
+def test_inverse_error_per_sample(gpu_device, case, reverse):
+    Z, Z32, xi = sl.reference(case, reverse)
+    cfg = (case, "zeros", True, False, "spectrum")
+    got = inverse(to_dev(Z32, gpu_device), cfg)
+    assert got.dtype == torch.float32 and tuple(got.shape) == xi.shape
+    e = sl.sample_error(got.cpu().numpy(), xi, case)
+    b, n = np.unravel_index(np.nanargmax(e) if not np.isnan(e).all() else 0, e.shape)
+    print(f"[stft_complex] inverse per sample {_id(cfg)} {'rising' if reverse else 'falling'}: "
+          f"max err {e.max():.3e} (shot {b}, sample {n} of {e.shape[1]}); normwise "
+          f"{normwise(got.cpu().numpy().astype(np.float64), xi):.3e}")
+    assert not np.isnan(e).any() and e.max() <= TOL, f"{e.max():.3e} > {TOL} at sample {n}"
 
 
 # Round trip: the boundary='zeros' configurations. The two detrended ones are left out: a

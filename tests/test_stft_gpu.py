@@ -185,7 +185,7 @@ def test_full_c2_batch_properties(gpu_device):
 
 
 @pytest.mark.parametrize("nperseg,noverlap,flags", [(256, 128, 7), (1024, 768, 7), (64, 16, 0),
-                                                    (512, 256, 1)])
+                                                    (512, 256, 1), (128, 64, 7), (128, 96, 0)])
 def test_fp16_samples_equal_fp32_path(gpu_device, nperseg, noverlap, flags):
     """specenh_stft_psd_f16 (fp16 samples widened on load, the C5 stream's input) is the
     same arithmetic as the fp32 path on the same values: bitwise-identical output, also
