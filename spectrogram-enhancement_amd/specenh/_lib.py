@@ -219,6 +219,15 @@ SIGNATURES_CSM = {
                                _c.c_void_p]),
 }
 
+# mode decomposition (batched Hermitian eigensolver); must match include/specenh_modes.h
+HERM_EIG_MAX_N = 64  # SPECENH_HERM_EIG_MAX_N
+HERM_EIG_MAX_SWEEPS = 16  # SPECENH_HERM_EIG_MAX_SWEEPS
+SIGNATURES_MODES = {
+    "specenh_herm_eig": (_c.c_int, [_c.c_void_p, _c.c_longlong, _c.c_longlong, _c.c_longlong,
+                                    _c.c_longlong, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                    _c.c_void_p]),
+}
+
 
 def lib():
     """Load (once) and return the ctypes handle; raise ExtensionNotLoaded on failure."""
@@ -238,7 +247,8 @@ def lib():
             raise ExtensionNotLoaded(f"failed to load {LIB_PATH}: {e}") from e
         dev_build = bool(os.environ.get("SPECENH_LIB"))
         for name, (res, args) in {**SIGNATURES, **SIGNATURES_STFT_COMPLEX,
-                                  **SIGNATURES_SPECTRAL, **SIGNATURES_CSM}.items():
+                                  **SIGNATURES_SPECTRAL, **SIGNATURES_CSM,
+                                  **SIGNATURES_MODES}.items():
             if dev_build and not hasattr(h, name):
                 continue  # an older revision's build for an A/B run (tools/build_rev_lib.sh)
             fn = getattr(h, name)

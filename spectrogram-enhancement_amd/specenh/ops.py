@@ -458,6 +458,77 @@ _op(f"csm_out(Tensor x, {_SP_ARGS}, Tensor(a!)? csm, Tensor(b!)? coh, Tensor(c!)
     "-> ()", _csm_out, lambda *a: None)
 
 
+# ---------------------------------------------------------------- Hermitian eigensolver
+def _eig_check(a, k):
+    if a.dtype != torch.complex64 or a.dim() < 2 or a.shape[-1] != a.shape[-2]:
+        raise ValueError("a must be complex64 [..., n, n]")
+    n = a.shape[-1]
+    if not 2 <= n <= _lib.HERM_EIG_MAX_N:
+        raise ValueError(f"n must be in [2, {_lib.HERM_EIG_MAX_N}], got {n}")
+    if not 0 <= k <= n:
+        raise ValueError(f"k must be in [0, {n}], got {k}")
+
+
+def _eig_layout(a):
+    """(a, count, matrix_stride): ``a`` as it is when every matrix is contiguous and the
+    leading axes step through memory by one stride >= n * n, else its contiguous copy."""
+    n = a.shape[-1]
+    lead = a.shape[:-2]
+    count = int(np.prod(lead, dtype=np.int64)) if lead else 1
+    ok = a.stride(-1) == 1 and a.stride(-2) == n
+    ms = n * n
+    dims = [(s, st) for s, st in zip(lead, a.stride()[:-2]) if s != 1]
+    if ok and count > 1 and dims:
+        ms = dims[-1][1]
+        for (_, st0), (s1, st1) in zip(dims[:-1], dims[1:]):
+            ok = ok and st0 == st1 * s1
+        ok = ok and ms >= n * n
+    if not ok:
+        a, ms = a.contiguous(), n * n
+    return a, count, ms
+
+
+def _herm_eig_out(a, k, w, v, sweeps):
+    _eig_check(a, k)
+    n, lead = a.shape[-1], tuple(a.shape[:-2])
+    if w is None and sweeps is None and k == 0:
+        raise ValueError("no output requested")
+    if k > 0 and v is None:
+        raise ValueError("v is needed for k > 0")
+    for o, shape, dt, name in ((w, lead + (n,), torch.float32, "w float32"),
+                               (v, lead + (k, n), torch.complex64, "v complex64"),
+                               (sweeps, lead, torch.int32, "sweeps int32")):
+        if o is not None and (tuple(o.shape) != shape or o.dtype != dt or not o.is_contiguous()
+                              or o.device != a.device):
+            raise ValueError(f"{name} must be contiguous {shape} on a's device")
+    a, count, ms = _eig_layout(a)
+    if count == 0:
+        return
+    _lib.check(_lib.lib().specenh_herm_eig(
+        _vp(a), count, n, ms, int(k), _vp(w), _vp(v if k > 0 else None), _vp(sweeps), _st(a)),
+        "herm_eig")
+
+
+def _herm_eig(a, k):
+    _eig_check(a, k)
+    n, lead = a.shape[-1], tuple(a.shape[:-2])
+    w = torch.empty(lead + (n,), dtype=torch.float32, device=a.device)
+    v = torch.empty(lead + (k, n), dtype=torch.complex64, device=a.device)
+    _herm_eig_out(a, k, w, v, None)
+    return w, v
+
+
+def _herm_eig_fake(a, k):
+    n, lead = a.shape[-1], tuple(a.shape[:-2])
+    return (a.new_empty(lead + (n,), dtype=torch.float32),
+            a.new_empty(lead + (k, n), dtype=torch.complex64))
+
+
+_op("herm_eig(Tensor a, int k) -> (Tensor, Tensor)", _herm_eig, _herm_eig_fake)
+_op("herm_eig_out(Tensor a, int k, Tensor(a!)? w, Tensor(b!)? v, Tensor(c!)? sweeps) -> ()",
+    _herm_eig_out, lambda *a: None)
+
+
 # ---------------------------------------------------------------- SVD denoiser
 def _bstride(A):
     """Batch stride for the C-ABI: a batch of one may carry any stride (e.g. 0 from a numpy

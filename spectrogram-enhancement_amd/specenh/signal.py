@@ -7,7 +7,8 @@ of csrc/stft_complex.hip through ``torch.ops.specenh``) and return float64 / com
 arrays of scipy's shapes. ``welch`` / ``csd`` / ``coherence`` run ``specenh.spectral`` (one
 fused launch of csrc/spectral_mean.hip; ``average='mean'`` only). ``cross_spectral_matrix``
 (not in scipy) gives ``csd`` / ``coherence`` of every channel pair of an array in one call
-(csrc/spectral_matrix.hip). There is no CPU fallback.
+(csrc/spectral_matrix.hip), ``array_modes`` the eigendecomposition of those matrices
+(csrc/herm_eig.hip). There is no CPU fallback.
 
 Differences from scipy, each one an exception rather than another result:
 ``nfft != nperseg``, two-sided spectra, axes other than the defaults, and the ``'even'``,
@@ -175,5 +176,41 @@ def cross_spectral_matrix(x, fs=1.0, window="hann", nperseg=None, noverlap=None,
     out = {}
     for name, v in est.items():
         v = v.cpu().numpy().astype(np.complex128 if name == "csm" else np.float64)
+        out[name] = v.reshape(lead + v.shape[1:])
+    return f, t, out
+
+
+def array_modes(x, k=1, fs=1.0, window="hann", nperseg=None, noverlap=None, nfft=None,
+                detrend="constant", return_onesided=True, scaling="density", axis=-1,
+                average="mean", navg=None):
+    """Mode decomposition of a channel array ``x[..., C, L]`` (not in scipy): one call of
+    ``specenh.spectral.array_modes``, the eigendecomposition of the cross-spectral matrix of
+    every frequency and averaging group (csrc/spectral_matrix.hip, csrc/herm_eig.hip).
+    Returns ``(f, t_groups, est)``: ``est["power"]`` float64 ``[..., F, G, C]``,
+    ``est["modes"]`` complex128 ``[..., F, G, k, C]`` and ``est["fraction"]`` float64
+    ``[..., F, G, k]``; the leading axes are flattened into the batch and restored."""
+    nperseg = 256 if nperseg is None else int(nperseg)
+    if nfft is not None and int(nfft) != nperseg:
+        raise NotImplementedError("nfft != nperseg is not supported on the GPU path")
+    if not return_onesided:
+        raise NotImplementedError("two-sided spectra are not supported on the GPU path")
+    if average != "mean":
+        if average == "median":
+            raise NotImplementedError("average='median' is not supported on the GPU path")
+        raise ValueError(f"average must be 'median' or 'mean', got {average}")
+    a = np.asarray(x)
+    if np.iscomplexobj(a):
+        raise NotImplementedError("complex input is not supported on the GPU path")
+    if a.ndim < 2:
+        raise ValueError("x must be at least 2-D: [..., channels, length]")
+    if axis not in (-1, a.ndim - 1):
+        raise NotImplementedError("only axis=-1 is supported on the GPU path")
+    xb, lead = _leading(np.array(a, dtype=np.float32, order="C"), 2)
+    f, t, est = _spectral.array_modes(
+        _upload(torch.from_numpy(xb)), k=k, fs=fs, window=window, nperseg=nperseg,
+        noverlap=noverlap, detrend=detrend, scaling=scaling, navg=navg)
+    out = {}
+    for name, v in est.items():
+        v = v.cpu().numpy().astype(np.complex128 if name == "modes" else np.float64)
         out[name] = v.reshape(lead + v.shape[1:])
     return f, t, out

@@ -18,7 +18,9 @@ raises ``NotImplementedError``.
 Channel arrays: ``cross_spectral_matrix`` / ``coherence_matrix`` give the Hermitian matrix of
 all channel pairs ``[B, F, G, C, C]`` in one call (csrc/spectral_matrix.hip through
 ``torch.ops.specenh.csm`` -> ``specenh_csm``): every frame is transformed once, then summed as
-a Gram product per frequency on the fp32 matrix cores.
+a Gram product per frequency on the fp32 matrix cores. ``array_modes`` / ``hermitian_modes``
+decompose those matrices (csrc/herm_eig.hip through ``torch.ops.specenh.herm_eig``): mode powers
+and the leading mode structures, without holding the matrices of the whole batch.
 """
 from __future__ import annotations
 
@@ -221,3 +223,101 @@ def coherence_matrix(x: torch.Tensor, fs: float = 1.0, window="hann", nperseg: i
     f, _, est = cross_spectral_matrix(x, fs, window, nperseg, noverlap, detrend, "density", None,
                                       ("coh",))
     return f, est["coh"][..., 0, :, :]
+
+
+# ---------------------------------------------------------------- mode decomposition
+def hermitian_modes(S: torch.Tensor, k: int = 1, return_sweeps: bool = False):
+    """Eigenvalues and the ``k`` leading eigenvectors of the Hermitian matrices
+    ``S[..., n, n]`` on a ROCm device (csrc/herm_eig.hip through ``torch.ops.specenh.herm_eig``:
+    cyclic Jacobi, one wave per matrix, ``2 <= n <= 64``).
+
+    Returns ``(w, v)``: ``w`` float32 ``[..., n]`` descending (not clamped at 0), ``v``
+    complex64 ``[..., k, n]``; ``v[..., m, :]`` is ``numpy.linalg.eigh``'s ``V[..., :, m]`` for
+    the same (descending) order, of unit norm, its component of largest modulus real positive.
+    Only the upper triangle and the real part of the diagonal are read; a matrix with a
+    non-finite element there gives NaN for that matrix alone. ``0 <= k <= n``. With
+    ``return_sweeps`` a third result: the Jacobi sweeps every matrix ran, int32 ``[...]``.
+    """
+    from .ops import ops
+    if not isinstance(S, torch.Tensor):
+        raise TypeError("S must be a torch.Tensor")
+    if not S.is_complex() or S.dim() < 2 or S.shape[-1] != S.shape[-2]:
+        raise ValueError("S must be complex [..., n, n]")
+    n = S.shape[-1]
+    if not 2 <= n <= _lib.HERM_EIG_MAX_N:
+        raise ValueError(f"n must be in [2, {_lib.HERM_EIG_MAX_N}], got {n}")
+    k = int(k)
+    if not 0 <= k <= n:
+        raise ValueError(f"k must be in [0, {n}], got {k}")
+    if S.device.type != "cuda":
+        raise RuntimeError("specenh.spectral runs on the GPU only (no CPU fallback); "
+                           "move the matrices to a ROCm device first")
+    if S.dtype != torch.complex64:
+        S = S.to(torch.complex64)
+    lead = tuple(S.shape[:-2])
+    w = torch.empty(lead + (n,), dtype=torch.float32, device=S.device)
+    v = torch.empty(lead + (k, n), dtype=torch.complex64, device=S.device)
+    sweeps = torch.empty(lead, dtype=torch.int32, device=S.device) if return_sweeps else None
+    ops.herm_eig_out(S, k, w, v, sweeps)
+    return (w, v, sweeps) if return_sweeps else (w, v)
+
+
+def array_modes(x: torch.Tensor, k: int = 1, fs: float = 1.0, window="hann", nperseg: int = 256,
+                noverlap=None, detrend="constant", scaling="density", navg=None):
+    """Mode decomposition of a channel array ``x[B, C, L]`` on a ROCm device: the
+    eigendecomposition of the cross-spectral matrix of every frequency and averaging group
+    (``cross_spectral_matrix`` then ``hermitian_modes``), without ever holding
+    ``[B, F, G, C, C]``: the batch runs in slices through one reused matrix buffer, sized so
+    that the slice's CSM workspace and its matrices each stay under ``CSM_WORKSPACE_CAP`` (a
+    single shot above it runs alone). Results do not depend on the split.
+
+    Returns ``(f, t_groups, est)``: ``est["power"]`` float32 ``[B, F, G, C]`` (the eigenvalues,
+    descending), ``est["modes"]`` complex64 ``[B, F, G, k, C]`` (the leading eigenvectors, the
+    conventions of ``hermitian_modes``), ``est["fraction"]`` float32 ``[B, F, G, k]`` =
+    ``power[..., :k] / power.sum(-1)`` (0/0 is NaN). ``1 <= k <= C``. ``x[C, L]`` drops ``B``.
+    """
+    from .ops import ops, csm_workspace, window_key
+    nperseg, noverlap = _check_nperseg(nperseg, noverlap)
+    sc, dt = _norm_scaling(scaling), _norm_detrend(detrend)
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("x must be a torch.Tensor")
+    if x.dim() not in (2, 3):
+        raise ValueError("x must be [batch, channels, length] or [channels, length]")
+    squeeze = x.dim() == 2
+    C, L = x.shape[-2], x.shape[-1]
+    if not 2 <= C <= _lib.CSM_MAX_CHANNELS:
+        raise ValueError(f"channels must be in [2, {_lib.CSM_MAX_CHANNELS}], got {C} "
+                         "(one channel: welch)")
+    k = int(k)
+    if not 1 <= k <= C:
+        raise ValueError(f"k must be in [1, {C}], got {k}")
+    if L < nperseg:
+        raise ValueError(f"signal of {L} samples is shorter than nperseg = {nperseg}")
+    navg = int(navg or 0)
+    T = (L - nperseg) // (nperseg - noverlap) + 1
+    if navg > T:
+        raise ValueError(f"navg = {navg} exceeds the number of frames ({T})")
+    if x.device.type != "cuda":
+        raise RuntimeError("specenh.spectral runs on the GPU only (no CPU fallback); "
+                           "move the signals to a ROCm device first")
+    x = _prep_array(x)
+    B = x.shape[0]
+    F, G = nperseg // 2 + 1, (1 if navg <= 0 else T // navg)
+    args = (nperseg, noverlap, window_key(window, nperseg), float(fs), sc, dt, navg)
+    power = torch.empty((B, F, G, C), dtype=torch.float32, device=x.device)
+    modes = torch.empty((B, F, G, k, C), dtype=torch.complex64, device=x.device)
+    # bytes a shot: the CSM workspace (spectra of every frame) and the matrices themselves
+    per_shot = max(8 * F * G * (navg if navg >= 1 else T) * C, 8 * F * G * C * C)
+    step = max(1, int(CSM_WORKSPACE_CAP) // per_shot)
+    if B:
+        ws = csm_workspace(x[:min(step, B)], *args)
+        buf = torch.empty((min(step, B), F, G, C, C), dtype=torch.complex64, device=x.device)
+    for b0 in range(0, B, step):
+        b1 = min(B, b0 + step)
+        ops.csm_out(x[b0:b1], *args, buf[:b1 - b0], None, ws)
+        ops.herm_eig_out(buf[:b1 - b0], k, power[b0:b1], modes[b0:b1], None)
+    est = {"power": power, "modes": modes,
+           "fraction": power[..., :k] / power.sum(-1, keepdim=True)}
+    if squeeze:
+        est = {name: v[0] for name, v in est.items()}
+    return frequencies(nperseg, fs), group_times(L, nperseg, noverlap, fs, navg), est
