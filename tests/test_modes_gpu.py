@@ -2,7 +2,10 @@
 decomposition built on it: parity with numpy.linalg.eigh in complex128 under the project's
 1e-5 contract, the output conventions, k selection, bitwise structure (batch position,
 stride, unread elements), special matrices (diagonal, zero, c I, a NaN that must stay in its
-matrix and must not keep the kernel busy), and array_modes end to end.
+matrix and must not keep the kernel busy), the output combinations of herm_eig_out, one launch
+of 100,003 2 x 2 matrices against the closed form, and array_modes end to end from 2 to 64
+channels. tests/test_modes_sizes_gpu.py runs every n, tests/test_modes_spectra_gpu.py other
+spectra and scales.
 
 Inputs are made on the CPU from a seeded generator, independent of the CSM kernels; every
 output buffer is NaN-filled before the launch. Each test prints measured against allowed
@@ -75,11 +78,12 @@ def check_conventions(v, label):
 
 
 def check_parity(S, w, v, wref, Vref, label):
-    """The 1e-5 contract relative to the truth's lambda_1 per matrix; S [m, n, n], w [m, n],
+    """The 1e-5 contract relative to the truth's spectral norm max |lambda| per matrix (written
+    l1: it is lambda_1 where the matrix is positive semidefinite); S [m, n, n], w [m, n],
     v [m, k, n] (eigenvectors as rows), wref [m, n], Vref [m, n, n] (columns)."""
     S = S.astype(np.complex128)
     k = v.shape[1]
-    l1 = wref[:, 0]
+    l1 = np.abs(wref).max(axis=1)
     assert np.isfinite(w).all() and np.isfinite(v.view(np.float32)).all()
     e_w = (np.abs(w - wref).max(axis=1) / l1).max()
     vc = np.swapaxes(v.astype(np.complex128), 1, 2)  # columns
@@ -215,10 +219,77 @@ def test_special_matrices(gpu_device, n):
     assert np.isnan(run(dev, S, 2)[0][3]).all()
 
 
-E2E = [(5, 256, 128, "hann", "linear", 2), (17, 64, 48, "hann", "linear", 5)]
+@pytest.mark.parametrize("n,T", [(5, 4), (33, 35)])
+def test_output_combinations_are_bitwise(gpu_device, n, T):
+    """Eigenvectors alone (w and sweeps absent) and eigenvalues alone (k = 0, an empty v, sweeps
+    absent) are the bits of the call with every output."""
+    dev = gpu_device
+    S = matrices(n, T)[0]
+    w, v, _ = run(dev, S, 2)
+    a = torch.from_numpy(np.array(S)).to(dev)
+    v1 = torch.full((M, 2, n), complex("nan+nanj"), dtype=torch.complex64, device=dev)
+    torch.ops.specenh.herm_eig_out(a, 2, None, v1, None)
+    w2 = torch.full((M, n), float("nan"), device=dev)
+    v2 = torch.empty((M, 0, n), dtype=torch.complex64, device=dev)
+    torch.ops.specenh.herm_eig_out(a, 0, w2, v2, None)
+    torch.cuda.synchronize()
+    assert np.isfinite(w).all() and np.isfinite(v.view(np.float32)).all()
+    assert np.array_equal(v1.cpu().numpy().view(np.float32), v.view(np.float32))
+    assert np.array_equal(w2.cpu().numpy(), w)
 
 
-@pytest.mark.parametrize("cfg", E2E, ids=["C5", "C17"])
+@functools.lru_cache(maxsize=None)
+def two_by_two(count, seed=2):
+    """`count` Hermitian 2 x 2 matrices [[a, b], [conj b, d]] in complex64 and their fp64 closed
+    form: lambda = (a + d) / 2 +- rho, rho = sqrt(((a - d) / 2)^2 + |b|^2); the eigenvector of
+    +rho is (delta + rho, conj b) for delta = (a - d) / 2 >= 0 and (b, rho - delta) otherwise
+    (the form without cancellation), that of -rho its orthogonal complement."""
+    rng = np.random.default_rng(seed)
+    S = np.zeros((count, 2, 2), np.complex64)
+    S[:, 0, 0], S[:, 1, 1] = rng.standard_normal(count), rng.standard_normal(count)
+    S[:, 0, 1] = rng.standard_normal(count) + 1j * rng.standard_normal(count)
+    S[:, 1, 0] = S[:, 0, 1].conj()
+    a, d = S[:, 0, 0].real.astype(np.float64), S[:, 1, 1].real.astype(np.float64)
+    b = S[:, 0, 1].astype(np.complex128)
+    delta = (a - d) / 2
+    rho = np.sqrt(delta ** 2 + np.abs(b) ** 2)
+    wref = np.stack([(a + d) / 2 + rho, (a + d) / 2 - rho], axis=1)
+    pos = delta >= 0
+    x = np.where(pos, delta + rho, b)
+    y = np.where(pos, b.conj(), rho - delta)
+    norm = np.sqrt(np.abs(x) ** 2 + np.abs(y) ** 2)
+    x, y = x / norm, y / norm
+    Vref = np.stack([np.stack([x, -y.conj()], axis=1), np.stack([y, x.conj()], axis=1)], axis=1)
+    for arr in (S, wref, Vref):
+        arr.setflags(write=False)
+    return S, wref, Vref
+
+
+def test_large_batch_of_2x2(gpu_device):
+    """100,003 matrices in one launch (25,001 workgroups of 4, the last one with 3 idle waves)
+    against the closed form, and three of them against single-matrix calls."""
+    count = 100_003
+    S, wref, Vref = two_by_two(count)
+    # the closed form is an eigendecomposition (the generator's own check, on the CPU)
+    S128 = S.astype(np.complex128)
+    assert np.abs(S128 @ Vref - Vref * wref[:, None, :]).max() <= 1e-12
+    assert np.abs(np.swapaxes(Vref, 1, 2).conj() @ Vref - np.eye(2)).max() <= 1e-12
+    w, v, sw = run(gpu_device, S, 2)
+    print(f"[2x2 count={count}] sweeps max {sw.max()}")
+    check_parity(S, w, v, wref, Vref, f"2x2 count={count}")
+    # one rotation stores a_pq = 0 exactly, so the second sweep finds nothing to rotate
+    assert (sw >= 1).all() and (sw <= 2).all()
+    for m in (0, 50_001, count - 1):
+        w1, v1, s1 = run(gpu_device, S[m:m + 1], 2)
+        assert np.array_equal(w1[0], w[m]) and s1[0] == sw[m]
+        assert np.array_equal(v1[0].view(np.float32), v[m].view(np.float32))
+
+
+E2E = [(5, 256, 128, "hann", "linear", 2), (17, 64, 48, "hann", "linear", 5),
+       (2, 64, 48, "hann", "linear", 0), (64, 64, 48, "hann", "constant", 3)]
+
+
+@pytest.mark.parametrize("cfg", E2E, ids=["C5", "C17", "C2", "C64"])
 def test_array_modes_end_to_end(gpu_device, cfg, monkeypatch):
     from test_csm_gpu import FS, signals
 
