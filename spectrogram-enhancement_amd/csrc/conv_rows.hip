@@ -567,16 +567,18 @@ void convt_rows_kernel(CRArgs a) {
   store_held();
 }
 
-// convt_rows_pw_kernel: convT1 (CO = 64 on 16-position rows), every wave with its OWN input
-// ring. The four waves of convt_rows_kernel<T, 64, 16> (one per 16-channel block) all read the
-// whole input row, so they shared one ring filled by two of them and met at a workgroup barrier
+// convt_rows_pw_store8_kernel (variant CONVT_STORE8; the default of rounds 4-6, kept as the A/B
+// and bitwise partner of convt_rows_pw_kernel below): convT1 (CO = 64 on 16-position rows),
+// every wave with its OWN input ring and 8-byte stores. The four waves of
+// convt_rows_kernel<T, 64, 16> (one per 16-channel block) all read the whole input row, so
+// they shared one ring filled by two of them and met at a workgroup barrier
 // every step. Here each wave LDS-DMAs the row (2 x 1 KB) into its own 8-row ring (18 KB; 72 KB
 // per workgroup, two workgroups per CU) and waits only for its own refill: no barrier in the
 // step loop, the two waves of a SIMD drift freely against each other. The input is read from
 // L2 four times instead of once (it is 32 KB per image against 128 KB of output).
 template <typename T, int LEAD>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2)))
-void convt_rows_pw_kernel(CRArgs a) {
+void convt_rows_pw_store8_kernel(CRArgs a) {
   static_assert(LEAD >= 1 && LEAD <= 4, "8-row ring: positions g .. g + 3 + LEAD live");
   using C = TC<64, 16>;
   constexpr int CO = 64, W = 16;
@@ -725,15 +727,229 @@ void convt_rows_pw_kernel(CRArgs a) {
   store_held();
 }
 
-// convt_rows_pg_kernel (variant CONVT_PG; measured SLOWER than convt_rows_pw_kernel, 0.148 vs
+// convt_rows_pw_kernel (convT1's default): the step's outputs staged in LDS and stored as whole
+// cache lines. The store8 kernel above wrote 8 bytes per lane: one store instruction touched 16
+// lines, 32 bytes each, and every 128-byte output pixel came from four unsynchronised waves;
+// with the stores taken out it ran 0.092 instead of 0.119 ms per 2048 shots. A
+// step's two output rows (2 x 32 pixels x 64 channels) are ONE contiguous 8 KB of the NHWC
+// output, so:
+//  * after relu_pack4 a wave writes its four 8-byte pieces per lane into an 8 KB tile in LDS
+//    (double-buffered: a wave may compute step g + 1 while another still stores step g). Piece
+//    u = 4 nb + kg of pixel (py, p = 2 m + px) sits at byte 4096 py + 128 p + 8 (u ^ m): the 16
+//    lanes of a ds_write_b64 group (one kg, m = 0 .. 15) cover all 32 banks once.
+//  * after the step's barrier wave w stores bytes 2048 w .. 2048 w + 2047 of the tile with two
+//    16-byte-per-lane instructions, each 1 KB contiguous (eight whole pixels). Lane l reads the
+//    16-byte chunk c = l & 7 of its pixel at chunk c ^ (m >> 1) (conflict-free under the
+//    ds_read_b128 lane groups) and swaps its halves when m is odd (m & 1 = (l >> 4) & 1).
+//  * the barrier being there anyway, the input ring is one per workgroup, filled by waves 0
+//    and 1 (convt_rows_kernel's scheme): 0.5 DMAs per wave-step instead of 2.
+//  * the step loop is unrolled by the ring length, so ring slots and tile buffers are immediate
+//    offsets; the tile's output offset and the refill's source row advance by scalar adds.
+// The outputs of step g are still stored at the start of step g + 1, ahead of that step's DMA.
+// The per-phase MFMA order is the store8 kernel's: bitwise equal.
+constexpr int CT_TILE = 2 * 32 * 64 * 2;  // bytes: two output rows of 32 pixels x 64 channels
+// (the tile maps are restated in tests/test_convt_stage_mapping.py)
+// the lane's piece of phase (0, 0); phase (py, px) adds 4096 py + 128 px
+__device__ __forceinline__ constexpr int ct_tile_write(int nb, int m, int kg) {
+  return 256 * m + 8 * ((4 * nb + kg) ^ m);
+}
+// where the 16 bytes of tile byte L = 2048 w + 1024 j + 16 l (wave w, lane l, store j) sit
+__device__ __forceinline__ constexpr int ct_tile_read(int w, int l, int j) {
+  const int L = 2048 * w + 1024 * j + 16 * l, p = (L >> 7) & 31;
+  return (L & ~0x70) | (((l & 7) ^ (p >> 2)) << 4);
+}
+
+template <typename T, int LEAD>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2)))
+void convt_rows_pw_kernel(CRArgs a) {
+  static_assert(LEAD >= 1 && LEAD <= 4, "8-row ring: positions g .. g + 3 + LEAD live");
+  using C = TC<64, 16>;
+  constexpr int W = 16;
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_st[];
+  unsigned char* const ring = lds_st;            // 8 input rows
+  unsigned char* const tile = lds_st + C::LDS;   // 2 output tiles
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int m = lane & 15, kg = lane >> 4;
+  const int nb = wv;
+  // units: whole images or row bands, as convt_rows_kernel's. Unit v = blockIdx.x + il G is
+  // rows v HB .. v HB + HB - 1 of the [N H] row stream (H = HB << lgb)
+  const int H = a.H, lgb = a.lgb, HB = H >> lgb, bmask = (1 << lgb) - 1;
+  const int SPI = HB + (lgb ? 2 : 1);
+  const int G = gridDim.x;
+  const int nimg = (((int)a.N << lgb) - (int)blockIdx.x + G - 1) / G;
+  const int S = nimg * SPI;
+
+  {
+    uint4* z = reinterpret_cast<uint4*>(ring);
+    for (int e = tid; e < C::LDS / 16; e += 256) z[e] = uint4{0u, 0u, 0u, 0u};
+  }
+  uint4 wf[50];  // tap fragments [phase][(dy, dx) taps][K half]
+  {
+    const T* __restrict__ Wg = reinterpret_cast<const T*>(a.w);
+    int u = 0;
+#pragma unroll
+    for (int ph = 0; ph < 4; ++ph)
+#pragma unroll
+      for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+        for (int dx = -1; dx <= 1; ++dx) {
+          if (!ttap(ph, dy, dx)) continue;
+#pragma unroll
+          for (int kh = 0; kh < 2; ++kh)
+            wf[u++] = *reinterpret_cast<const uint4*>(
+                Wg + (((16 * nb + m) * 5 + tky(ph >> 1, dy)) * 5 + tky(ph & 1, dx)) * 64 +
+                32 * kh + 8 * kg);
+        }
+  }
+  const f32x4 bias = f32x4{a.b[16 * nb + 4 * kg], a.b[16 * nb + 4 * kg + 1],
+                           a.b[16 * nb + 4 * kg + 2], a.b[16 * nb + 4 * kg + 3]};
+  resident_loads_landed();
+  int xo[3];  // byte offset of pixel m + dx (stored + 1), group kg, in a ring row
+#pragma unroll
+  for (int dx = -1; dx <= 1; ++dx) {
+    const int ps = m + dx + 1;
+    xo[dx + 1] = ps * 128 + 16 * (kg ^ (ps & 7));
+  }
+  // per-lane tile addresses: the wave's four pieces, its two read-back chunks, their place in
+  // the 8 KB of output
+  unsigned char* const tw = tile + ct_tile_write(nb, m, kg);
+  const unsigned char* const tr0 = tile + ct_tile_read(wv, lane, 0);
+  const unsigned char* const tr1 = tile + ct_tile_read(wv, lane, 1);
+  const unsigned swp = 0u - ((lane >> 4) & 1);  // all ones: swap the chunk's halves
+  const unsigned vo = 2048u * wv + 16u * lane;
+  // ring refill: wave w < 2 moves chunks 64 w .. 64 w + 63 of a row
+  const T* __restrict__ X = reinterpret_cast<const T*>(a.x);
+  const bool dma_wave = wv < C::DMA_WAVES;
+  int dsrc = 0;
+  if (dma_wave) {
+    const int c = 64 * wv + lane;
+    const int ps = 1 + c / 8, gs = c & 7;
+    dsrc = (ps - 1) * 64 + 8 * (gs ^ (ps & 7));
+  }
+  // stream position il SPI + q -> ring slot `slot`: row q - 1 of unit v (il-th of the
+  // workgroup); rows outside the image are the zero rows
+  auto stage_at = [&](int slot, int il, int v, int q) __attribute__((always_inline)) -> bool {
+    if (!dma_wave) return false;
+    unsigned char* dst = ring + slot * C::ROWB + 128 + 1024 * wv;
+    const int r = (v & bmask) * HB + q - 1;
+    if (il < nimg && r >= 0 && r < H) {
+      lds_dma16_s(X + (long long)(v * HB + q - 1) * (W * 64), 2u * dsrc, dst);
+      return true;
+    }
+    *reinterpret_cast<uint4*>(dst + 16 * lane) = uint4{0u, 0u, 0u, 0u};
+    return false;
+  };
+  __syncthreads();  // ring zeroed
+#pragma unroll
+  for (int p = 0; p < 3 + LEAD; ++p) {
+    const int il = p / SPI;
+    stage_at(p & 7, il, (int)blockIdx.x + il * G, p - il * SPI);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  lds_barrier();
+
+  unsigned char* const Ob = reinterpret_cast<unsigned char*>(a.out);
+  bool held = false;     // (wave-uniform) a tile waits in LDS for its stores
+  unsigned hob = 0;      // its byte offset in the output (host-checked < 2^32)
+  int vmn = 0;           // this wave's vector-memory ops issued in the loop
+  int mk[LEAD + 1];      // vmn right after the DMA of position g + 3 + i (-1: none in flight)
+#pragma unroll
+  for (int i = 0; i <= LEAD; ++i) mk[i] = -1;
+  // the held tile (buffer at byte tb of the tile area) -> output: two 1 KB stores per wave
+  auto store_held = [&](int tb) __attribute__((always_inline)) {
+    if (held) {
+      uint4 v0 = *reinterpret_cast<const uint4*>(tr0 + tb);
+      uint4 v1 = *reinterpret_cast<const uint4*>(tr1 + tb);
+      // (halves swapped where m is odd: bit selects, no exec-masked region in the step)
+      auto sel = [&](unsigned x, unsigned y) { return (x & ~swp) | (y & swp); };
+      v0 = uint4{sel(v0.x, v0.z), sel(v0.y, v0.w), sel(v0.z, v0.x), sel(v0.w, v0.y)};
+      v1 = uint4{sel(v1.x, v1.z), sel(v1.y, v1.w), sel(v1.z, v1.x), sel(v1.w, v1.y)};
+      gstore16_s<0>(Ob + hob, vo, v0);
+      gstore16_s<1024>(Ob + hob, vo, v1);
+      vmn += 2;
+    }
+  };
+  // scalar counters: step g is row s of unit il, its tile at output byte tob; its refill
+  // position g + 3 + LEAD is row sp - 1 of unit vp (the ilp-th)
+  const unsigned ustride = (unsigned)G * HB * CT_TILE;
+  int s = 0;
+  unsigned tob = (unsigned)blockIdx.x * HB * CT_TILE, ub = tob;
+  int ilp = (3 + LEAD) / SPI, sp = 3 + LEAD - ilp * SPI, vp = (int)blockIdx.x + ilp * G;
+  // step g with g & 7 == I: ring slots and tile buffers are compile-time
+  auto step = [&](auto ic) __attribute__((always_inline)) {
+    constexpr int I = decltype(ic)::value;
+    store_held(((I + 1) & 1) * CT_TILE);
+    held = false;
+    mk[LEAD] = stage_at((I + 3 + LEAD) & 7, ilp, vp, sp) ? ++vmn : -1;
+    if (s < HB) {
+      f32x4 acc[4] = {bias, bias, bias, bias};
+      int u0[4] = {0, 8, 20, 32};
+#pragma unroll
+      for (int dy = -1; dy <= 1; ++dy) {
+        const unsigned char* src = ring + ((I + 1 + dy) & 7) * C::ROWB;
+#pragma unroll
+        for (int dx = -1; dx <= 1; ++dx) {
+          // K half 1 (groups kg + 4) sits at the half-0 offset ^ 64 bytes (swizzle bit 2)
+          const uint4 b0 = *reinterpret_cast<const uint4*>(src + xo[dx + 1]);
+          const uint4 b1 = *reinterpret_cast<const uint4*>(src + (xo[dx + 1] ^ 64));
+#pragma unroll
+          for (int ph = 0; ph < 4; ++ph)
+            if (ttap(ph, dy, dx)) acc[ph] = mfma<T>(wf[u0[ph]], b0, acc[ph]);
+#pragma unroll
+          for (int ph = 0; ph < 4; ++ph)
+            if (ttap(ph, dy, dx)) {
+              acc[ph] = mfma<T>(wf[u0[ph] + 1], b1, acc[ph]);
+              u0[ph] += 2;
+            }
+        }
+      }
+#pragma unroll
+      for (int ph = 0; ph < 4; ++ph)
+        *reinterpret_cast<uint2*>(tw + (I & 1) * CT_TILE + 4096 * (ph >> 1) + 128 * (ph & 1)) =
+            relu_pack4<T>(acc[ph]);
+      hob = tob;
+      held = true;
+    }
+    // position g + 3 has landed (waves 0 and 1; steady state: 3 steps of 2 stores + 1 DMA
+    // younger than it); the barrier also publishes the tile
+    if (mk[0] >= 0) wait_vmcnt_ss<9>(vmn - mk[0]);
+    lds_barrier();
+#pragma unroll
+    for (int i = 0; i < LEAD; ++i) mk[i] = mk[i + 1];
+    tob += CT_TILE;
+    if (++s == SPI) { s = 0; ub += ustride; tob = ub; }
+    if (++sp == SPI) { sp = 0; ++ilp; vp += G; }
+  };
+  for (int g = 0; g < S; g += 8) {
+    step(std::integral_constant<int, 0>{});
+    if (g + 1 >= S) break;
+    step(std::integral_constant<int, 1>{});
+    if (g + 2 >= S) break;
+    step(std::integral_constant<int, 2>{});
+    if (g + 3 >= S) break;
+    step(std::integral_constant<int, 3>{});
+    if (g + 4 >= S) break;
+    step(std::integral_constant<int, 4>{});
+    if (g + 5 >= S) break;
+    step(std::integral_constant<int, 5>{});
+    if (g + 6 >= S) break;
+    step(std::integral_constant<int, 6>{});
+    if (g + 7 >= S) break;
+    step(std::integral_constant<int, 7>{});
+  }
+  store_held(((S - 1) & 1) * CT_TILE);
+}
+
+// convt_rows_pg_kernel (variant CONVT_PG; measured SLOWER than convt_rows_pw_store8_kernel, 0.148 vs
 // 0.130 ms per 2048 shots, profiles/r05_convt1_pg_ab.txt: kept for the record of the trial):
 // convT1 with the four output phases split over two waves per 16-channel
 // block (8 waves, one workgroup per CU): wave group A runs phases (0,0) and (1,1) (4 + 9 taps),
 // group B phases (0,1) and (1,0) (6 + 6), so a wave holds 26 or 24 tap fragments (~100 VGPRs)
 // instead of 50 and has the registers to read all of a step's B fragments (18 / 16) before its
-// MFMAs: convt_rows_pw_kernel read them in pairs right before use, exposing an LDS round trip
-// per neighbourhood offset (PMC: MFMA busy 0.35). Each wave keeps its own input ring (LDS-DMA,
-// no barrier in the step loop), as convt_rows_pw_kernel.
+// MFMAs: convt_rows_pw_store8_kernel read them in pairs right before use, exposing an LDS round
+// trip per neighbourhood offset (PMC: MFMA busy 0.35). Each wave keeps its own input ring
+// (LDS-DMA, no barrier in the step loop), as convt_rows_pw_store8_kernel.
 template <typename T, int LEAD>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2)))
 void convt_rows_pg_kernel(CRArgs a) {
@@ -916,11 +1132,14 @@ int convt_row_bands_lg(int N, int H, long long slots) {
   return lg;
 }
 
-template <typename T>
+// convT1's per-workgroup-of-4-waves kernels: staged whole-line stores (default) or the per-wave
+// rings with 8-byte stores (STORE8)
+template <typename T, bool STORE8>
 hipError_t launch_convt_rows_pw(const CRArgs& a0, hipStream_t st) {
   using C = TC<64, 16>;
-  constexpr int LDS = 4 * C::RING * C::ROWB;
-  const void* k = reinterpret_cast<const void*>(&convt_rows_pw_kernel<T, 3>);
+  constexpr int LDS = STORE8 ? 4 * C::RING * C::ROWB : C::LDS + 2 * CT_TILE;
+  const void* k = STORE8 ? reinterpret_cast<const void*>(&convt_rows_pw_store8_kernel<T, 3>)
+                         : reinterpret_cast<const void*>(&convt_rows_pw_kernel<T, 3>);
   static int per_cu[64] = {};
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
@@ -937,7 +1156,10 @@ hipError_t launch_convt_rows_pw(const CRArgs& a0, hipStream_t st) {
   CRArgs a = a0;
   a.lgb = convt_row_bands_lg(a.N, a.H, slots);
   const long long grid = std::min<long long>((long long)a.N << a.lgb, slots);
-  SPECENH_LAUNCH((convt_rows_pw_kernel<T, 3>), dim3((unsigned)grid), dim3(256), LDS, st, a);
+  if constexpr (STORE8)
+    SPECENH_LAUNCH((convt_rows_pw_store8_kernel<T, 3>), dim3((unsigned)grid), dim3(256), LDS, st, a);
+  else
+    SPECENH_LAUNCH((convt_rows_pw_kernel<T, 3>), dim3((unsigned)grid), dim3(256), LDS, st, a);
   return hipGetLastError();
 }
 
@@ -1776,8 +1998,12 @@ int convt_rows(int dtype, const void* x, int N, int H, int W, int CI, const void
   if (CI != 64 || K != 5) return SPECENH_OK;
   if (CO == 64 && W == 16 && variant(V_CONVT_SHARED_RING) == 0 && variant(V_CONVT_PG) != 0)
     e = f16 ? launch_convt_rows_pg<_Float16>(a, st) : launch_convt_rows_pg<__bf16>(a, st);
+  else if (CO == 64 && W == 16 && variant(V_CONVT_SHARED_RING) == 0 && variant(V_CONVT_STORE8) != 0)
+    e = f16 ? launch_convt_rows_pw<_Float16, true>(a, st)
+            : launch_convt_rows_pw<__bf16, true>(a, st);
   else if (CO == 64 && W == 16 && variant(V_CONVT_SHARED_RING) == 0)
-    e = f16 ? launch_convt_rows_pw<_Float16>(a, st) : launch_convt_rows_pw<__bf16>(a, st);
+    e = f16 ? launch_convt_rows_pw<_Float16, false>(a, st)
+            : launch_convt_rows_pw<__bf16, false>(a, st);
   else if (CO == 64 && W == 16)
     e = f16 ? launch_convt_rows<_Float16, 64, 16>(a, st) : launch_convt_rows<__bf16, 64, 16>(a, st);
   else if (CO == 32 && W == 32)

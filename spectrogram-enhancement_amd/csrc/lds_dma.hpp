@@ -44,6 +44,19 @@ __device__ __forceinline__ void gstore8(void* dst, uint2 v) {
   asm volatile("global_store_dwordx2 %0, %1, off" : : "v"(dst), "v"(v) : "memory");
 }
 
+// one 16-byte global store per lane, likewise ONE counted instruction, at a wave-uniform base
+// (SGPR pair) + a 32-bit per-lane byte offset + the immediate OFF: a kernel whose store
+// address advances uniformly keeps the lane part in one register for the whole launch
+template <int OFF>
+__device__ __forceinline__ void gstore16_s(void* sbase, unsigned voff, uint4 v) {
+  static_assert(OFF >= 0 && OFF < 4096, "13-bit signed immediate");
+  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));  // (a register tuple for "v")
+  asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3"
+               :
+               : "v"(voff), "v"(__builtin_bit_cast(u32x4, v)), "s"(sbase), "n"(OFF)
+               : "memory");
+}
+
 // The launch-resident fragments (weights, biases) loaded before a step loop have landed:
 // s_waitcnt vmcnt(0) as the builtin, which the compiler's wait insertion sees. Without it the
 // compiler puts its wait for those loads at their first use INSIDE the loop, where it runs
