@@ -12,6 +12,9 @@ scipy-compatible time-averaged spectra (Welch PSD, CSD, coherence, coherogram):
 cross-spectral matrix and coherence matrix of a channel array (every pair in one call):
   specenh.signal.cross_spectral_matrix (numpy); specenh.spectral.cross_spectral_matrix,
   coherence_matrix (device tensors)
+bispectrum and squared bicoherence (three-wave coupling, auto and cross):
+  specenh.signal.bicoherence (numpy); specenh.bispectrum.bispectrum, bicoherence,
+  bispectrum_from_spectra, summed_bicoherence (device tensors)
 Device fast paths: specgr_batch, denoise_batch, cross_spectrogram_batch, and
 specenh.autograd (differentiable Conv2D / Conv2DTranspose / MaxPooling2D / BCE).
 Every one of them reaches the HIP kernels through the ``torch.ops.specenh`` operators

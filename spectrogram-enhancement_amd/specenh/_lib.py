@@ -228,6 +228,23 @@ SIGNATURES_MODES = {
                                     _c.c_void_p]),
 }
 
+# bispectrum and squared bicoherence; must match include/specenh_bispectrum.h
+BISPEC_BISPEC, BISPEC_BICOH = 1, 2  # operator output mask
+SIGNATURES_BISPECTRUM = {
+    "specenh_bispectrum_workspace_bytes": (_c.c_size_t, [_c.c_void_p, _c.c_longlong,
+                                                         _c.c_longlong, _c.c_longlong,
+                                                         _c.c_longlong]),
+    "specenh_bispectrum": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                      _c.c_longlong, _c.c_longlong, _c.c_longlong,
+                                      _c.c_longlong, _c.c_longlong, _c.c_longlong,
+                                      _c.c_longlong, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                      _c.c_size_t, _c.c_void_p]),
+    "specenh_bispectrum_spectra": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                              _c.c_longlong, _c.c_longlong, _c.c_longlong,
+                                              _c.c_longlong, _c.c_longlong, _c.c_void_p,
+                                              _c.c_void_p, _c.c_void_p]),
+}
+
 
 def lib():
     """Load (once) and return the ctypes handle; raise ExtensionNotLoaded on failure."""
@@ -248,7 +265,7 @@ def lib():
         dev_build = bool(os.environ.get("SPECENH_LIB"))
         for name, (res, args) in {**SIGNATURES, **SIGNATURES_STFT_COMPLEX,
                                   **SIGNATURES_SPECTRAL, **SIGNATURES_CSM,
-                                  **SIGNATURES_MODES}.items():
+                                  **SIGNATURES_MODES, **SIGNATURES_BISPECTRUM}.items():
             if dev_build and not hasattr(h, name):
                 continue  # an older revision's build for an A/B run (tools/build_rev_lib.sh)
             fn = getattr(h, name)

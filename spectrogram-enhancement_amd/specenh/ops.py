@@ -458,6 +458,189 @@ _op(f"csm_out(Tensor x, {_SP_ARGS}, Tensor(a!)? csm, Tensor(b!)? coh, Tensor(c!)
     "-> ()", _csm_out, lambda *a: None)
 
 
+# ---------------------------------------------------------------- bispectrum, bicoherence
+_BISPEC_DTYPES = (torch.complex64, torch.float32)
+
+
+def _bispec_bins(F, nbins):
+    K = F if nbins <= 0 else int(nbins)
+    if not 1 <= K <= F:
+        raise ValueError(f"nbins must be in [1, {F}], got {nbins}")
+    return K
+
+
+def _bispec_shape(x, nperseg, noverlap, navg, nbins):
+    T = (x.shape[1] - nperseg) // (nperseg - noverlap) + 1
+    K = _bispec_bins(nperseg // 2 + 1, nbins)
+    return x.shape[0], _sp_groups(T, navg), K, K
+
+
+def _bispec_check(x, y, z, nperseg, noverlap, navg):
+    for name, v in (("x", x), ("y", y), ("z", z)):
+        if v is not None and (v.dim() != 2 or v.stride(1) != 1 or v.dtype != torch.float32):
+            raise ValueError(f"{name} must be float32 [batch, length] with unit stride along "
+                             "length")
+        if v is not None and (v.shape != x.shape or v.device != x.device):
+            raise ValueError("x, y and z must have the same shape and device")
+    if noverlap >= nperseg:
+        raise ValueError("noverlap must be less than nperseg.")
+    B, L = x.shape
+    if L < nperseg:
+        raise ValueError("signal shorter than nperseg")
+    T = (L - nperseg) // (nperseg - noverlap) + 1
+    if navg > T:
+        raise ValueError(f"navg = {navg} exceeds the number of frames ({T})")
+
+
+def _bispec_stride(v):
+    """Batch stride of v[B, L]; the stride of a one-element axis is free."""
+    s = v.stride(0) if v.shape[0] > 1 else v.shape[1]
+    if s < v.shape[1]:
+        raise ValueError("a signal must not overlap itself: batch stride >= length")
+    return s
+
+
+def _bispec_distinct(x, y, z):
+    """Number of distinct signals among x, y, z, as specenh_bispectrum counts them."""
+    seen = [(x.data_ptr(), _bispec_stride(x))]
+    for v in (y, z):
+        if v is not None and (v.data_ptr(), _bispec_stride(v)) not in seen:
+            seen.append((v.data_ptr(), _bispec_stride(v)))
+    return len(seen)
+
+
+def _bispec_need(x, nsig, nperseg, noverlap, window, fs, scaling, detrend, navg):
+    from . import stft
+    plan = stft.get_plan_key(x.device, nperseg, noverlap, window, fs, scaling, detrend, 0.0)
+    B, L = x.shape
+    need = int(_lib.lib().specenh_bispectrum_workspace_bytes(plan.handle, B, nsig, L, int(navg)))
+    if need == 0 and B > 0:
+        _lib.check(_lib.SPECENH_EINVAL, "bispectrum_workspace_bytes")
+    return plan, need
+
+
+def bispectrum_workspace(x, y, z, nperseg, noverlap, window, fs, scaling, detrend, navg):
+    """A workspace for ``bispectrum_out`` on ``x[B, L]`` (and ``y``, ``z``; uint8, from torch's
+    caching allocator): the spectra of every frame that enters a group of every distinct
+    signal, ``8 B nsignals T F`` bytes."""
+    _bispec_check(x, y, z, nperseg, noverlap, navg)
+    _, need = _bispec_need(x, _bispec_distinct(x, y, z), nperseg, noverlap, window, fs, scaling,
+                           detrend, navg)
+    return torch.empty(max(need, 1), dtype=torch.uint8, device=x.device)
+
+
+def _bispec_outputs(outs, shape, device):
+    if all(o is None for o in outs):
+        raise ValueError("no output requested")
+    for o, dt in zip(outs, _BISPEC_DTYPES):
+        if o is not None and (tuple(o.shape) != shape or o.dtype != dt or not o.is_contiguous()
+                              or o.device != device):
+            raise ValueError(f"outputs must be contiguous {shape} on x's device (bispec "
+                             "complex64, bicoh float32)")
+
+
+def _bispectrum_out(x, y, z, nperseg, noverlap, window, fs, scaling, detrend, navg, nbins, bispec,
+                    bicoh, workspace):
+    _bispec_check(x, y, z, nperseg, noverlap, navg)
+    shape = _bispec_shape(x, nperseg, noverlap, navg, nbins)
+    _bispec_outputs((bispec, bicoh), shape, x.device)
+    nsig = _bispec_distinct(x, y, z)
+    plan, need = _bispec_need(x, nsig, nperseg, noverlap, window, fs, scaling, detrend, navg)
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=x.device)
+    if (workspace.device != x.device or not workspace.is_contiguous()
+            or workspace.numel() * workspace.element_size() < need or workspace.data_ptr() % 16):
+        raise ValueError(f"workspace must be a contiguous, 16-byte aligned buffer of at least "
+                         f"{need} bytes on x's device")
+    B, L = x.shape
+    _lib.check(_lib.lib().specenh_bispectrum(
+        plan.handle, _vp(x), _vp(y), _vp(z), B, L, _bispec_stride(x),
+        0 if y is None else _bispec_stride(y), 0 if z is None else _bispec_stride(z), int(navg),
+        shape[2], _vp(bispec), _vp(bicoh), _vp(workspace),
+        workspace.numel() * workspace.element_size(), _st(x)), "bispectrum")
+
+
+def _bispectrum(x, y, z, nperseg, noverlap, window, fs, scaling, detrend, navg, nbins, outputs):
+    _bispec_check(x, y, z, nperseg, noverlap, navg)
+    if not outputs & 3:
+        raise ValueError("no output requested")
+    shape = _bispec_shape(x, nperseg, noverlap, navg, nbins)
+    outs = [torch.empty(shape, dtype=dt, device=x.device) if outputs >> i & 1 else None
+            for i, dt in enumerate(_BISPEC_DTYPES)]
+    _bispectrum_out(x, y, z, nperseg, noverlap, window, fs, scaling, detrend, navg, nbins, *outs,
+                    None)
+    return tuple(x.new_empty((0,), dtype=dt) if o is None else o
+                 for o, dt in zip(outs, _BISPEC_DTYPES))
+
+
+def _bispectrum_fake(x, y, z, nperseg, noverlap, window, fs, scaling, detrend, navg, nbins,
+                     outputs):
+    shape = _bispec_shape(x, nperseg, noverlap, navg, nbins)
+    return tuple(x.new_empty(shape if outputs >> i & 1 else (0,), dtype=dt)
+                 for i, dt in enumerate(_BISPEC_DTYPES))
+
+
+def _bispec_spectra_shape(X, navg, nbins):
+    B, T, F = X.shape
+    if T < 1:
+        raise ValueError("the spectra must hold at least one frame")
+    if navg > T:
+        raise ValueError(f"navg = {navg} exceeds the number of frames ({T})")
+    return B, _sp_groups(T, navg), _bispec_bins(F, nbins), _bispec_bins(F, nbins)
+
+
+def _bispec_spectra_check(X, Y, Z):
+    for name, v in (("X", X), ("Y", Y), ("Z", Z)):
+        if v is not None and (v.dim() != 3 or v.dtype != torch.complex64
+                              or not v.is_contiguous()):
+            raise ValueError(f"{name} must be contiguous complex64 [batch, frames, F]")
+        if v is not None and (v.shape != X.shape or v.device != X.device):
+            raise ValueError("X, Y and Z must have the same shape and device")
+    if not 1 <= X.shape[2] <= 2049:
+        raise ValueError(f"F must be in [1, 2049], got {X.shape[2]}")
+
+
+def _bispectrum_spectra_out(X, Y, Z, navg, nbins, bispec, bicoh):
+    _bispec_spectra_check(X, Y, Z)
+    shape = _bispec_spectra_shape(X, navg, nbins)
+    _bispec_outputs((bispec, bicoh), shape, X.device)
+    B, T, F = X.shape
+    same = X.data_ptr()  # the same spectra under another tensor: the auto case
+    _lib.check(_lib.lib().specenh_bispectrum_spectra(
+        _vp(X), _vp(None if Y is None or Y.data_ptr() == same else Y),
+        _vp(None if Z is None or Z.data_ptr() == same else Z), B, T, F, int(navg), shape[2],
+        _vp(bispec), _vp(bicoh), _st(X)), "bispectrum_spectra")
+
+
+def _bispectrum_spectra(X, Y, Z, navg, nbins, outputs):
+    _bispec_spectra_check(X, Y, Z)
+    if not outputs & 3:
+        raise ValueError("no output requested")
+    shape = _bispec_spectra_shape(X, navg, nbins)
+    outs = [torch.empty(shape, dtype=dt, device=X.device) if outputs >> i & 1 else None
+            for i, dt in enumerate(_BISPEC_DTYPES)]
+    _bispectrum_spectra_out(X, Y, Z, navg, nbins, *outs)
+    return tuple(X.new_empty((0,), dtype=dt) if o is None else o
+                 for o, dt in zip(outs, _BISPEC_DTYPES))
+
+
+def _bispectrum_spectra_fake(X, Y, Z, navg, nbins, outputs):
+    shape = _bispec_spectra_shape(X, navg, nbins)
+    return tuple(X.new_empty(shape if outputs >> i & 1 else (0,), dtype=dt)
+                 for i, dt in enumerate(_BISPEC_DTYPES))
+
+
+_op(f"bispectrum(Tensor x, Tensor? y, Tensor? z, {_SP_ARGS}, int nbins, int outputs) -> "
+    "(Tensor, Tensor)", _bispectrum, _bispectrum_fake)
+_op(f"bispectrum_out(Tensor x, Tensor? y, Tensor? z, {_SP_ARGS}, int nbins, "
+    "Tensor(a!)? bispec, Tensor(b!)? bicoh, Tensor(c!)? workspace) -> ()", _bispectrum_out,
+    lambda *a: None)
+_op("bispectrum_spectra(Tensor X, Tensor? Y, Tensor? Z, int navg, int nbins, int outputs) -> "
+    "(Tensor, Tensor)", _bispectrum_spectra, _bispectrum_spectra_fake)
+_op("bispectrum_spectra_out(Tensor X, Tensor? Y, Tensor? Z, int navg, int nbins, "
+    "Tensor(a!)? bispec, Tensor(b!)? bicoh) -> ()", _bispectrum_spectra_out, lambda *a: None)
+
+
 # ---------------------------------------------------------------- Hermitian eigensolver
 def _eig_check(a, k):
     if a.dtype != torch.complex64 or a.dim() < 2 or a.shape[-1] != a.shape[-2]:

@@ -8,7 +8,8 @@ arrays of scipy's shapes. ``welch`` / ``csd`` / ``coherence`` run ``specenh.spec
 fused launch of csrc/spectral_mean.hip; ``average='mean'`` only). ``cross_spectral_matrix``
 (not in scipy) gives ``csd`` / ``coherence`` of every channel pair of an array in one call
 (csrc/spectral_matrix.hip), ``array_modes`` the eigendecomposition of those matrices
-(csrc/herm_eig.hip). There is no CPU fallback.
+(csrc/herm_eig.hip), ``bicoherence`` (not in scipy) the squared bicoherence of one to three
+signals (csrc/bispectrum.hip). There is no CPU fallback.
 
 Differences from scipy, each one an exception rather than another result:
 ``nfft != nperseg``, two-sided spectra, axes other than the defaults, and the ``'even'``,
@@ -21,6 +22,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from . import bispectrum as _bispectrum
 from . import spectral as _spectral
 from . import stft as _stft
 
@@ -214,3 +216,29 @@ def array_modes(x, k=1, fs=1.0, window="hann", nperseg=None, noverlap=None, nfft
         v = v.cpu().numpy().astype(np.complex128 if name == "modes" else np.float64)
         out[name] = v.reshape(lead + v.shape[1:])
     return f, t, out
+
+
+def bicoherence(x, y=None, z=None, fs=1.0, window="hann", nperseg=None, noverlap=None,
+                detrend="constant", nbins=None):
+    """The squared bicoherence ``|<X_k Y_l conj(Z_{k+l})>|^2 / (<|X_k Y_l|^2> <|Z_{k+l}|^2>)``
+    of the whole signal (not in scipy: one call of ``specenh.bispectrum.bicoherence``,
+    csrc/bispectrum.hip); ``y`` and ``z`` default to ``x``. Returns ``(f[:K], b2)``, ``b2``
+    float64 ``[..., K, K]`` with ``K = nbins`` (default ``nperseg // 2 + 1``), 0 where
+    ``k + l > nperseg // 2``; the leading axes are flattened into the batch and restored."""
+    nperseg = 256 if nperseg is None else int(nperseg)
+    arrs = [np.asarray(v) for v in (x, y, z) if v is not None]
+    for a in arrs:
+        if np.iscomplexobj(a):
+            raise NotImplementedError("complex input is not supported on the GPU path")
+        if a.ndim == 0:
+            raise ValueError("x must be at least 1-D")
+        if a.shape != arrs[0].shape:
+            raise ValueError("x, y and z must have the same shape")
+    lead = arrs[0].shape[:-1]
+    ts = [None if v is None else
+          _upload(torch.from_numpy(_leading(np.array(v, dtype=np.float32, order="C"), 1)[0]))
+          for v in (x, y, z)]
+    f, b2 = _bispectrum.bicoherence(ts[0], ts[1], ts[2], fs=fs, window=window, nperseg=nperseg,
+                                    noverlap=noverlap, detrend=detrend, nbins=nbins)
+    b2 = b2.cpu().numpy().astype(np.float64)
+    return f, b2.reshape(lead + b2.shape[1:])
