@@ -9,7 +9,7 @@
 //
 // bispectrum_transform_kernel: a workgroup owns S consecutive frames of one signal of one
 //   shot. It loads them into LDS, detrends (fp64 sums) and windows them, transforms them side
-//   by side (the passes of fft_real.hpp, one real frame per N/2-point FFT) and writes 2 X,
+//   by side (all of it fft_lds.hpp, one real frame per N/2-point FFT) and writes 2 X,
 //   unscaled, to the workspace as float2 [shot][signal][frame][F]: frame-major with the bins
 //   contiguous, what the second kernel streams. Every frame of every distinct signal is
 //   transformed exactly once; y or z that alias another signal share its spectra.
@@ -41,14 +41,12 @@
 #include "specenh_bispectrum.h"
 #include "runtime.hpp"
 #include "stft_plan.hpp"
-#include "fft_real.hpp"
+#include "fft_lds.hpp"
 
 namespace specenh {
-int set_error(int code, const std::string& msg);  // stft_psd.hip
-
 namespace {
 
-using namespace fft_real;  // c_mul, wave_sum, fft_half, unpack2
+using namespace fft_lds;  // load_frames, stockham, unpack2, nyquist2
 
 constexpr int CT = 256;  // threads per workgroup (both kernels)
 constexpr int CHUNK = SPECENH_SPECTRAL_CHUNK;
@@ -59,9 +57,6 @@ constexpr int FS = 8;     // frames staged at once
 constexpr int ROW = 256;  // float2 a staged frame takes: X 64 | Y 64 | Z 127 (+ 1 unused)
 static_assert(CHUNK % FS == 0, "a chunk is a whole number of staging steps");
 static_assert(2 * TILE + 2 * TILE - 1 <= ROW && ROW == CT, "one staged element per thread");
-
-// Frames transformed side by side: 8 where two buffers of S * N/2 complex fit 64 KiB.
-inline int slots_for(int N) { return N <= 1024 ? 8 : 8192 / N; }
 
 struct Signals {
   const float* p[3];   // distinct signals; shot b of signal s at p[s] + b * stride[s]
@@ -90,39 +85,11 @@ __global__ __launch_bounds__(CT) void bispectrum_transform_kernel(TransformArgs 
   const int t0 = blockIdx.x * S, sg = blockIdx.y;
   const long long b = blockIdx.z;
   const float* xb = a.sig.p[sg] + b * a.sig.stride[sg];
-  const float kc = 0.5f * (N - 1);
-  for (int idx = tid; idx < S * N; idx += CT) {
-    const int s = idx >> a.log2n, n = idx & (N - 1);
-    float v = 0.f;  // slots past the last frame stay zero and are not stored
-    if (t0 + s < a.Tu) v = xb[(long long)(t0 + s) * a.hop + n];
-    if (a.detrend == SPECENH_DETREND_NONE) v *= a.win[n];
-    raw[idx] = v;
-  }
-  __syncthreads();
-  if (a.detrend != SPECENH_DETREND_NONE) {  // uniform; fp64 sums, one wave per slot
-    for (int s = tid >> 6; s < S; s += CT / 64) {
-      double sx = 0.0, skx = 0.0;
-      for (int n = tid & 63; n < N; n += 64) {
-        const double v = raw[s * N + n];
-        sx += v;
-        skx += ((double)n - 0.5 * (N - 1)) * v;
-      }
-      sx = wave_sum(sx);
-      skx = wave_sum(skx);
-      if ((tid & 63) == 0) {
-        const double skk = (double)N * ((double)N * N - 1.0) / 12.0;
-        stat[s][0] = (float)(sx / N);
-        stat[s][1] = a.detrend == SPECENH_DETREND_LINEAR ? (float)(skx / skk) : 0.f;
-      }
-    }
-    __syncthreads();
-    for (int idx = tid; idx < S * N; idx += CT) {
-      const int s = idx >> a.log2n, n = idx & (N - 1);
-      raw[idx] = (raw[idx] - stat[s][0] - stat[s][1] * ((float)n - kc)) * a.win[n];
-    }
-    __syncthreads();
-  }
-  const float2* res = fft_half<CT>(bufA, bufB, M, log2m, S, a.tw, tid);
+  load_frames<CT>(raw, stat, N, a.log2n, S, a.detrend, a.win, tid, [&](int s, int n) {
+    // slots past the last frame stay zero and are not stored
+    return t0 + s < a.Tu ? xb[(long long)(t0 + s) * a.hop + n] : 0.f;
+  });
+  const float2* res = stockham<CT>(bufA, bufB, M, log2m, S, a.tw, N, tid);
   // bins fastest: consecutive lanes store consecutive float2 of a frame's row
   const long long F = M + 1;
   float2* wb = a.ws + ((b * a.nsig + sg) * a.Tu + t0) * F;  // slot s, bin k at wb + s * F + k
@@ -131,10 +98,7 @@ __global__ __launch_bounds__(CT) void bispectrum_transform_kernel(TransformArgs 
     if (t0 + s >= a.Tu) continue;
     wb[s * F + k] = unpack2(res + s * M, k, M, a.tw[k]);
   }
-  if (tid < S && t0 + tid < a.Tu) {  // 2 X_{N/2} = 2 (Re Z_0 - Im Z_0), real
-    const float2 z0 = res[tid * M];
-    wb[tid * F + M] = make_float2(2.f * (z0.x - z0.y), 0.f);
-  }
+  if (tid < S && t0 + tid < a.Tu) wb[tid * F + M] = make_float2(nyquist2(res + tid * M), 0.f);
 }
 
 struct AccumulateArgs {
@@ -288,45 +252,13 @@ __global__ __launch_bounds__(CT) void bispectrum_accumulate_kernel(AccumulateArg
   }
 }
 
-// N >= 1024 takes 64 KiB of dynamic LDS next to the static stat[]: the attribute, once per
-// device
-hipError_t allow_lds() {
-  static bool done[64] = {};
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  if (dev >= 0 && dev < 64 && done[dev]) return hipSuccess;
-  e = hipFuncSetAttribute((const void*)bispectrum_transform_kernel,
-                          hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS);
-  if (e == hipSuccess && dev >= 0 && dev < 64) done[dev] = true;
-  return e;
-}
+LdsOptIn g_lds;  // N >= 1024 takes 64 KiB of dynamic LDS next to the static stat[]
 
-int ilog2i(int n) {
-  int l = 0;
-  while ((1 << l) < n) ++l;
-  return l;
-}
-
-// frames, groups, frames per group and frames that enter a group of a call, or a negative
-// error; validates everything but the pointers
-struct Split {
-  long long T, G, glen, Tu;
-};
+// the split of a call, or a negative error; validates everything but the pointers
 int split_for(const specenh_stft_plan* plan, long long batch, long long length, long long navg,
-              Split* s) {
+              FrameSplit* s) {
   if (batch < 0) return set_error(SPECENH_EINVAL, "batch must be >= 0");
-  const int N = plan->nperseg;
-  if (N < 64 || N > 4096 || (N & (N - 1)))
-    return set_error(SPECENH_EUNSUPPORTED, "nperseg must be a power of two in [64, 4096]");
-  s->T = specenh_stft_frames(length, N, plan->noverlap);
-  if (s->T < 0) return (int)s->T;
-  s->G = specenh_spectral_groups(s->T, navg);
-  if (s->G < 0) return (int)s->G;
-  if (s->T > (1ll << 30)) return set_error(SPECENH_EINVAL, "too many frames");
-  s->glen = navg >= 1 ? navg : s->T;
-  s->Tu = s->G * s->glen;
-  return SPECENH_OK;
+  return frame_split(plan, length, navg, true, s);
 }
 
 // the accumulate launches of a call: shots [0, batch) in steps of grid.y
@@ -361,7 +293,7 @@ size_t specenh_bispectrum_workspace_bytes(const specenh_stft_plan* plan, long lo
                                           long long nsignals, long long length,
                                           long long navg) {
   using namespace specenh;
-  Split s;
+  FrameSplit s;
   if (!plan) {
     set_error(SPECENH_EINVAL, "null plan");
     return 0;
@@ -383,7 +315,7 @@ int specenh_bispectrum(const specenh_stft_plan* plan, const float* x, const floa
   using namespace specenh;
   if (!plan) return set_error(SPECENH_EINVAL, "null plan");
   if (!x) return set_error(SPECENH_EINVAL, "null x");
-  Split s;
+  FrameSplit s;
   const int rc = split_for(plan, batch, length, navg, &s);
   if (rc != SPECENH_OK) return rc;
   if (x_stride < length) return set_error(SPECENH_EINVAL, "x_stride < length");
@@ -419,14 +351,14 @@ int specenh_bispectrum(const specenh_stft_plan* plan, const float* x, const floa
     return set_error(SPECENH_EINVAL, "workspace must be 16-byte aligned");
   if (workspace_bytes < specenh_bispectrum_workspace_bytes(plan, batch, nsig, length, navg))
     return set_error(SPECENH_EINVAL, "workspace too small");
-  hipError_t e = allow_lds();
+  hipError_t e = allow_lds(g_lds, {(const void*)bispectrum_transform_kernel}, MAX_LDS);
   if (e != hipSuccess)
     return set_error(SPECENH_EHIP, std::string("bispectrum: ") + hipGetErrorString(e));
   TransformArgs t{};
   t.sig = sig;
   t.nsig = nsig;
   t.N = N; t.log2n = ilog2i(N); t.hop = plan->hop;
-  t.S = slots_for(N); t.detrend = plan->detrend;
+  t.S = slots8_for(N); t.detrend = plan->detrend;
   t.Tu = (int)s.Tu;
   t.win = plan->d_window; t.tw = plan->d_tw_nat;
   const size_t lds = (size_t)t.S * N * sizeof(float2);  // two buffers of S * N/2

@@ -31,7 +31,6 @@
 #include "runtime.hpp"
 
 namespace specenh {
-int set_error(int code, const std::string& msg);  // stft_psd.hip
 
 namespace {
 

@@ -41,7 +41,6 @@
 #include "runtime.hpp"
 
 namespace specenh {
-int set_error(int code, const std::string& msg);  // stft_psd.hip
 
 namespace {
 

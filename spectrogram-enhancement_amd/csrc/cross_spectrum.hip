@@ -16,8 +16,8 @@
 // One workgroup per (frame, signal pair). Both real frames ride in one complex FFT,
 // z = x_w + i*y_w, and separate afterwards: X_k = (Z_k + conj Z_{N-k}) / 2,
 // Y_k = (Z_k - conj Z_{N-k}) / 2i. Detrend sums in fp64 (wave butterflies + LDS);
-// FFT = mixed-radix Stockham (one radix-2 pass when log2 N is odd, then radix-4) in LDS
-// ping-pong buffers, twiddles W_N^t from a plan table.
+// FFT = the mixed-radix Stockham passes of fft_lds.hpp, one transform per workgroup, twiddles
+// W_N^t from this plan's own table.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -26,11 +26,11 @@
 
 #include "specenh.h"
 #include "runtime.hpp"
+#include "fft_lds.hpp"
 
 struct specenh_stft_plan;
 
 namespace specenh {
-int set_error(int code, const std::string& msg);  // stft_psd.hip
 int stft_csd_amplitude(const specenh_stft_plan* plan, const float* x, const float* y,
                        long long batch, long long length, long long x_stride, long long y_stride,
                        float* out, hipStream_t stream, bool* launched);  // stft_psd.hip
@@ -63,15 +63,7 @@ struct CsdArgs {
   void* out;  // mode 0: float2 [B][F][T]; mode 1: float |Pxy| [B][F][T]
 };
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
-
-__device__ __forceinline__ float2 c_mul(float2 a, float2 w) {
-  return make_float2(fmaf(a.x, w.x, -a.y * w.y), fmaf(a.x, w.y, a.y * w.x));
-}
+using namespace fft_lds;  // wave_sum, stockham
 
 __global__ __launch_bounds__(CT) void csd_kernel(CsdArgs a) {
   extern __shared__ float2 sm[];  // 2 x N complex
@@ -79,7 +71,6 @@ __global__ __launch_bounds__(CT) void csd_kernel(CsdArgs a) {
   const int N = a.N, t = blockIdx.x, tid = threadIdx.x;
   const long long b = blockIdx.y;
   float2* src = sm;
-  float2* dst = sm + N;
   const float* xb = a.x + b * a.xs + (long long)t * a.step;
   const float* yb = a.y + b * a.ys + (long long)t * a.step;
   const double kc = 0.5 * (N - 1);
@@ -117,42 +108,7 @@ __global__ __launch_bounds__(CT) void csd_kernel(CsdArgs a) {
     src[n] = make_float2((v.x - mx - bx * k) * w, (v.y - my - by * k) * w);
   }
   __syncthreads();
-  // ---- Stockham autosort FFT: natural order in, natural order out ----
-  int Ns = 1;
-  if (a.log2n & 1) {
-    for (int j = tid; j < N / 2; j += CT) {
-      const float2 v0 = src[j], v1 = src[j + N / 2];
-      dst[2 * j] = make_float2(v0.x + v1.x, v0.y + v1.y);
-      dst[2 * j + 1] = make_float2(v0.x - v1.x, v0.y - v1.y);
-    }
-    float2* tmp = src; src = dst; dst = tmp;
-    Ns = 2;
-    __syncthreads();
-  }
-  for (; Ns < N; Ns *= 4) {
-    const int q = N / 4, tstep = N / (4 * Ns);
-    for (int j = tid; j < q; j += CT) {
-      const int jm = j & (Ns - 1);
-      float2 v0 = src[j], v1 = src[j + q], v2 = src[j + 2 * q], v3 = src[j + 3 * q];
-      if (jm) {
-        const int e = jm * tstep;
-        v1 = c_mul(v1, a.tw[e]);
-        v2 = c_mul(v2, a.tw[2 * e]);
-        v3 = c_mul(v3, a.tw[(3 * e) & (N - 1)]);
-      }
-      const float2 s02 = make_float2(v0.x + v2.x, v0.y + v2.y);
-      const float2 d02 = make_float2(v0.x - v2.x, v0.y - v2.y);
-      const float2 s13 = make_float2(v1.x + v3.x, v1.y + v3.y);
-      const float2 d13 = make_float2(v1.x - v3.x, v1.y - v3.y);  // -i * d13 = (d13.y, -d13.x)
-      const int o = (j - jm) * 4 + jm;
-      dst[o] = make_float2(s02.x + s13.x, s02.y + s13.y);
-      dst[o + Ns] = make_float2(d02.x + d13.y, d02.y - d13.x);
-      dst[o + 2 * Ns] = make_float2(s02.x - s13.x, s02.y - s13.y);
-      dst[o + 3 * Ns] = make_float2(d02.x - d13.y, d02.y + d13.x);
-    }
-    float2* tmp = src; src = dst; dst = tmp;
-    __syncthreads();
-  }
+  src = stockham<CT>(src, sm + N, N, a.log2n, 1, a.tw, N, tid);
   // ---- separate X, Y; Pxy = conj(X) Y * scale, one-sided doubling ----
   const int F = N / 2 + 1;
   for (int k = tid; k < F; k += CT) {
@@ -204,8 +160,7 @@ int specenh_csd_plan_create(specenh_csd_plan** plan, int nperseg, int noverlap,
   p->noverlap = noverlap;
   p->step = N - noverlap;
   p->detrend = detrend;
-  p->log2n = 0;
-  while ((1 << p->log2n) < N) ++p->log2n;
+  p->log2n = specenh::ilog2i(N);
   p->scale = (float)(scaling == SPECENH_SCALING_DENSITY ? 1.0 / (fs * s2) : 1.0 / (s1 * s1));
   hipError_t e = hipGetDevice(&p->device);
   if (e == hipSuccess) e = hipMalloc(&p->d_window, N * sizeof(float));

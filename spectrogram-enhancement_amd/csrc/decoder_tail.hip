@@ -43,7 +43,6 @@
 #include "runtime.hpp"
 
 namespace specenh {
-int set_error(int code, const std::string& msg);  // stft_psd.hip
 
 namespace {
 

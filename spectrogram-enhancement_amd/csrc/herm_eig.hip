@@ -41,7 +41,6 @@
 #include "specenh_modes.h"
 
 namespace specenh {
-int set_error(int code, const std::string& msg);  // stft_psd.hip
 
 namespace {
 
@@ -302,18 +301,7 @@ inline int row_stride(int P) {
   return P + PAD[P / 2 - 1];
 }
 
-template <int U>
-hipError_t allow_lds() {
-  static bool done[64] = {};
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  if (dev >= 0 && dev < 64 && done[dev]) return hipSuccess;
-  e = hipFuncSetAttribute((const void*)herm_eig_kernel<U>,
-                          hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS);
-  if (e == hipSuccess && dev >= 0 && dev < 64) done[dev] = true;
-  return e;
-}
+LdsOptIn g_lds[2];  // herm_eig_kernel<4>, <8>
 
 }  // namespace
 }  // namespace specenh
@@ -347,7 +335,8 @@ int specenh_herm_eig(const void* a, long long count, long long n, long long matr
   const size_t lds = (size_t)g.mpw * g.lds_per;
   if (lds > (size_t)MAX_LDS) return set_error(SPECENH_EUNSUPPORTED, "matrix does not fit LDS");
   const bool wide = (g.P + g.L - 1) / g.L > 4;  // elements a lane has in a pass
-  hipError_t e = wide ? allow_lds<8>() : allow_lds<4>();
+  hipError_t e = allow_lds(g_lds[wide], {wide ? (const void*)herm_eig_kernel<8>
+                                              : (const void*)herm_eig_kernel<4>}, MAX_LDS);
   if (e != hipSuccess)
     return set_error(SPECENH_EHIP, std::string("herm_eig: ") + hipGetErrorString(e));
   const long long step = (1ll << 30);  // matrices per launch (grid.x < 2^31)

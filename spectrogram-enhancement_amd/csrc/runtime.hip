@@ -10,8 +10,6 @@
 #include "specenh.h"
 
 namespace specenh {
-int set_error(int code, const std::string& msg);  // stft_psd.hip
-
 namespace {
 
 struct VariantName {
@@ -76,6 +74,21 @@ int device_cus() {
     c = 256;
   g_cus[dev].store(c, std::memory_order_relaxed);  // same value from any racing thread
   return c;
+}
+
+hipError_t allow_lds(LdsOptIn& site, std::initializer_list<const void*> kernels, int bytes) {
+  static_assert(sizeof(site.done) / sizeof(site.done[0]) == kMaxDevices, "one flag per device");
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  const bool known = dev >= 0 && dev < kMaxDevices;
+  if (known && site.done[dev].load(std::memory_order_acquire)) return hipSuccess;
+  for (const void* k : kernels) {
+    e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) return e;
+  }
+  if (known) site.done[dev].store(true, std::memory_order_release);  // racing threads set the same
+  return hipSuccess;
 }
 
 void note_launch(const void* kernel) { g_ring[g_launches++ % kRing] = kernel; }

@@ -1,5 +1,6 @@
-// runtime.hpp — host-side runtime shared by the kernel files: kernel-variant switches,
-// the per-device CU count for persistent grids, and the record of the last launched kernel.
+// runtime.hpp — host-side runtime shared by the kernel files: the error record, kernel-variant
+// switches, the per-device CU count for persistent grids, the opt-in to large dynamic LDS, and
+// the record of the last launched kernel.
 //
 // Variant switches select between kernels that compute the same result (A/B tests and the
 // per-layer tools). They are read from the environment ONCE per process (SPECENH_<NAME>,
@@ -9,7 +10,21 @@
 
 #include <hip/hip_runtime.h>
 
+#include <atomic>
+#include <initializer_list>
+#include <string>
+
 namespace specenh {
+
+// record `msg` as the calling thread's last error and return `code` (stft_psd.hip)
+int set_error(int code, const std::string& msg);
+
+// log2 of a power of two (rounded up otherwise)
+inline int ilog2i(int n) {
+  int l = 0;
+  while ((1 << l) < n) ++l;
+  return l;
+}
 
 enum Variant : int {
   V_CONVT_PAIR = 0,   // Conv2DTranspose forward in (tile, row-phase) workgroups (opt-in)
@@ -59,6 +74,14 @@ int variant(Variant v);
 
 // CU count of the calling thread's current HIP device, queried once per device
 int device_cus();
+
+// Dynamic LDS above the default needs an attribute on each kernel: set it to `bytes` for
+// `kernels` on the calling thread's device, once per device and call site (`site`: the call
+// site's flags, a zero-initialised static). A later call is one hipGetDevice and one load.
+struct LdsOptIn {
+  std::atomic<bool> done[64];
+};
+hipError_t allow_lds(LdsOptIn& site, std::initializer_list<const void*> kernels, int bytes);
 
 // record `kernel` (the host stub a launch used) as the calling thread's last launch:
 // specenh_last_kernel_name() reports its symbol, so a measurement can key PMC counters by

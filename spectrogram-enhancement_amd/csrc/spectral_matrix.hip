@@ -8,9 +8,9 @@
 //
 // csm_transform_kernel: a workgroup owns one frame of one shot and S consecutive channels.
 //   It loads the S frames into LDS, detrends (fp64 sums) and windows them, transforms them
-//   side by side (one real frame per N/2-point Stockham FFT and the unpack of
-//   fft_real.hpp, nothing shared between two channels) and writes 2 X to the workspace
-//   as float2 [shot][bin][frame][C]. The channel blocks of one frame are neighbouring
+//   side by side (all of it fft_lds.hpp: one real frame per N/2-point Stockham FFT, then the
+//   unpack, nothing shared between two channels) and writes 2 X to the workspace as float2
+//   [shot][bin][frame][C]. The channel blocks of one frame are neighbouring
 //   workgroups, so a workspace row is completed within a short time. Every frame of every
 //   channel is transformed exactly once.
 //
@@ -41,11 +41,9 @@
 #include "specenh_csm.h"
 #include "runtime.hpp"
 #include "stft_plan.hpp"
-#include "fft_real.hpp"
+#include "fft_lds.hpp"
 
 namespace specenh {
-int set_error(int code, const std::string& msg);  // stft_psd.hip
-
 namespace {
 
 constexpr int CT = 256;  // threads per workgroup (both kernels)
@@ -55,10 +53,7 @@ constexpr int MAX_LDS = 64 * 1024;
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-// Channels transformed side by side: 8 where two buffers of S * N/2 complex fit 64 KiB.
-inline int slots_for(int N) { return N <= 1024 ? 8 : 8192 / N; }
-
-using namespace fft_real;  // c_mul, wave_sum, fft_half, unpack2
+using namespace fft_lds;  // load_frames, stockham, unpack2, nyquist2
 
 struct TransformArgs {
   const float* x;          // shot b, channel c at x + b * bs + c * cs
@@ -83,39 +78,11 @@ __global__ __launch_bounds__(CT) void csm_transform_kernel(TransformArgs a) {
   const long long tu = blockIdx.x / a.nblk, b = blockIdx.z;
   const int c0 = (int)(blockIdx.x - tu * a.nblk) * S;
   const float* xb = a.x + b * a.bs + tu * a.hop;
-  const float kc = 0.5f * (N - 1);
-  for (int idx = tid; idx < S * N; idx += CT) {
-    const int s = idx >> a.log2n, n = idx & (N - 1);
-    float v = 0.f;  // slots past the last channel stay zero and are not stored
-    if (c0 + s < C) v = xb[(long long)(c0 + s) * a.cs + n];
-    if (a.detrend == SPECENH_DETREND_NONE) v *= a.win[n];
-    raw[idx] = v;
-  }
-  __syncthreads();
-  if (a.detrend != SPECENH_DETREND_NONE) {  // uniform; fp64 sums, one wave per slot
-    for (int s = tid >> 6; s < S; s += CT / 64) {
-      double sx = 0.0, skx = 0.0;
-      for (int n = tid & 63; n < N; n += 64) {
-        const double v = raw[s * N + n];
-        sx += v;
-        skx += ((double)n - 0.5 * (N - 1)) * v;
-      }
-      sx = wave_sum(sx);
-      skx = wave_sum(skx);
-      if ((tid & 63) == 0) {
-        const double skk = (double)N * ((double)N * N - 1.0) / 12.0;
-        stat[s][0] = (float)(sx / N);
-        stat[s][1] = a.detrend == SPECENH_DETREND_LINEAR ? (float)(skx / skk) : 0.f;
-      }
-    }
-    __syncthreads();
-    for (int idx = tid; idx < S * N; idx += CT) {
-      const int s = idx >> a.log2n, n = idx & (N - 1);
-      raw[idx] = (raw[idx] - stat[s][0] - stat[s][1] * ((float)n - kc)) * a.win[n];
-    }
-    __syncthreads();
-  }
-  const float2* res = fft_half<CT>(bufA, bufB, M, log2m, S, a.tw, tid);
+  load_frames<CT>(raw, stat, N, a.log2n, S, a.detrend, a.win, tid, [&](int s, int n) {
+    // slots past the last channel stay zero and are not stored
+    return c0 + s < C ? xb[(long long)(c0 + s) * a.cs + n] : 0.f;
+  });
+  const float2* res = stockham<CT>(bufA, bufB, M, log2m, S, a.tw, N, tid);
   // channels fastest: S consecutive lanes store S consecutive float2 of a workspace row
   const long long F = M + 1;
   float2* wb = a.ws + (b * F * a.Tu + tu) * C;  // bin k at wb + k * Tu * C
@@ -126,10 +93,8 @@ __global__ __launch_bounds__(CT) void csm_transform_kernel(TransformArgs a) {
     const float2 X = unpack2(res + s * M, k, M, a.tw[k]);
     wb[k * kstep + c0 + s] = X;
   }
-  if (tid < S && c0 + tid < C) {  // 2 X_{N/2} = 2 (Re Z_0 - Im Z_0), real
-    const float2 z0 = res[tid * M];
-    wb[M * kstep + c0 + tid] = make_float2(2.f * (z0.x - z0.y), 0.f);
-  }
+  if (tid < S && c0 + tid < C)
+    wb[M * kstep + c0 + tid] = make_float2(nyquist2(res + tid * M), 0.f);
 }
 
 struct GramArgs {
@@ -256,47 +221,15 @@ __global__ __launch_bounds__(CT) void csm_gram_kernel(GramArgs a) {
   }
 }
 
-// N >= 1024 takes 64 KiB of dynamic LDS next to the static stat[]: the attribute, once per
-// device
-hipError_t allow_lds() {
-  static bool done[64] = {};
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  if (dev >= 0 && dev < 64 && done[dev]) return hipSuccess;
-  e = hipFuncSetAttribute((const void*)csm_transform_kernel,
-                          hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS);
-  if (e == hipSuccess && dev >= 0 && dev < 64) done[dev] = true;
-  return e;
-}
+LdsOptIn g_lds;  // N >= 1024 takes 64 KiB of dynamic LDS next to the static stat[]
 
-int ilog2i(int n) {
-  int l = 0;
-  while ((1 << l) < n) ++l;
-  return l;
-}
-
-// frames, groups, frames per group and frames that enter a group of a call, or a negative
-// error; validates everything but the pointers
-struct Split {
-  long long T, G, glen, Tu;
-};
+// the split of a call, or a negative error; validates everything but the pointers
 int split_for(const specenh_stft_plan* plan, long long batch, long long channels,
-              long long length, long long navg, Split* s) {
+              long long length, long long navg, FrameSplit* s) {
   if (batch < 0) return set_error(SPECENH_EINVAL, "batch must be >= 0");
   if (channels < 2 || channels > SPECENH_CSM_MAX_CHANNELS)
     return set_error(SPECENH_EINVAL, "channels must be in [2, 64]");
-  const int N = plan->nperseg;
-  if (N < 64 || N > 4096 || (N & (N - 1)))
-    return set_error(SPECENH_EUNSUPPORTED, "nperseg must be a power of two in [64, 4096]");
-  s->T = specenh_stft_frames(length, N, plan->noverlap);
-  if (s->T < 0) return (int)s->T;
-  s->G = specenh_spectral_groups(s->T, navg);
-  if (s->G < 0) return (int)s->G;
-  if (s->T > (1ll << 30)) return set_error(SPECENH_EINVAL, "too many frames");
-  s->glen = navg >= 1 ? navg : s->T;
-  s->Tu = s->G * s->glen;
-  return SPECENH_OK;
+  return frame_split(plan, length, navg, true, s);
 }
 
 }  // namespace
@@ -307,7 +240,7 @@ extern "C" {
 size_t specenh_csm_workspace_bytes(const specenh_stft_plan* plan, long long batch,
                                    long long channels, long long length, long long navg) {
   using namespace specenh;
-  Split s;
+  FrameSplit s;
   if (!plan) {
     set_error(SPECENH_EINVAL, "null plan");
     return 0;
@@ -324,7 +257,7 @@ int specenh_csm(const specenh_stft_plan* plan, const float* x, long long batch,
   using namespace specenh;
   if (!plan) return set_error(SPECENH_EINVAL, "null plan");
   if (!x) return set_error(SPECENH_EINVAL, "null x");
-  Split s;
+  FrameSplit s;
   const int rc = split_for(plan, batch, channels, length, navg, &s);
   if (rc != SPECENH_OK) return rc;
   if (channel_stride < length) return set_error(SPECENH_EINVAL, "channel_stride < length");
@@ -342,15 +275,15 @@ int specenh_csm(const specenh_stft_plan* plan, const float* x, long long batch,
   const int ntp = C <= TILE ? 1 : 3;
   const long long per_shot = s.G * F * ntp;  // waves of the Gram kernel
   if (per_shot > (1ll << 31)) return set_error(SPECENH_EUNSUPPORTED, "too many groups");
-  if (s.Tu * ((C + slots_for(N) - 1) / slots_for(N)) > 2147483647LL)
+  if (s.Tu * ((C + slots8_for(N) - 1) / slots8_for(N)) > 2147483647LL)
     return set_error(SPECENH_EUNSUPPORTED, "too many frames");
-  hipError_t e = allow_lds();
+  hipError_t e = allow_lds(g_lds, {(const void*)csm_transform_kernel}, MAX_LDS);
   if (e != hipSuccess)
     return set_error(SPECENH_EHIP, std::string("csm: ") + hipGetErrorString(e));
   TransformArgs t{};
   t.bs = batch_stride; t.cs = channel_stride;
   t.C = C; t.N = N; t.log2n = ilog2i(N); t.hop = plan->hop;
-  t.S = slots_for(N); t.log2s = ilog2i(t.S); t.detrend = plan->detrend;
+  t.S = slots8_for(N); t.log2s = ilog2i(t.S); t.detrend = plan->detrend;
   t.Tu = (int)s.Tu; t.nblk = (C + t.S - 1) / t.S;
   t.win = plan->d_window; t.tw = plan->d_tw_nat;
   const size_t lds = (size_t)t.S * N * sizeof(float2);  // two buffers of S * N/2

@@ -10,8 +10,8 @@
 //
 // One real frame per transform, nothing shared between two frames or two signals: a frame of
 // N reals is read as N/2 complex numbers z_j = v_2j + i v_2j+1, transformed by an N/2-point
-// Stockham FFT (the LDS ping-pong passes of stft_complex.hip with the plan's natural-order
-// twiddles at stride 2) and unpacked,
+// Stockham FFT (the LDS ping-pong passes of fft_lds.hpp with the plan's natural-order
+// twiddles at stride 2, after that header's frame front end) and unpacked,
 //   X_k = E_k + W_N^k O_k,  2 E_k = Z_k + conj Z_{N/2-k},  2 O_k = -i (Z_k - conj Z_{N/2-k}).
 // That is the butterfly count of carrying two real frames in one N-point transform, without
 // x's rounding reaching y (or frame 2q's reaching 2q+1): the coherence inherits the pointwise
@@ -28,11 +28,9 @@
 #include "specenh_spectral.h"
 #include "runtime.hpp"
 #include "stft_plan.hpp"
-#include "fft_real.hpp"
+#include "fft_lds.hpp"
 
 namespace specenh {
-int set_error(int code, const std::string& msg);  // stft_psd.hip
-
 namespace {
 
 constexpr int CT = 256;  // threads per workgroup
@@ -47,7 +45,7 @@ constexpr int MAX_LDS = 64 * 1024;
 // Transforms side by side: 256 radix-4 butterflies a pass where N allows, at least x and y.
 inline int slots_for(int N) { return N >= 1024 ? 2 : 2048 / N; }
 
-using namespace fft_real;  // c_mul, wave_sum, fft_half, unpack2
+using namespace fft_lds;  // load_frames, stockham, unpack2, nyquist2
 
 struct Outputs {
   float* pxx;
@@ -100,7 +98,6 @@ __global__ __launch_bounds__(CT) void spectral_mean_kernel(Args a) {
   const int cnt = left < CHUNK ? left : CHUNK;  // >= 1
   const float* xb = a.x + b * a.xs;
   const float* yb = PAIR ? a.y + b * a.ys : nullptr;
-  const float kc = 0.5f * (N - 1);
   // bins 0 .. M-1 of this thread's slots; the Nyquist bin of all of them (k = 0 threads only)
   float acc[NI][NA], accn[NA];
 #pragma unroll
@@ -110,40 +107,13 @@ __global__ __launch_bounds__(CT) void spectral_mean_kernel(Args a) {
     for (int i = 0; i < NI; ++i) acc[i][j] = 0.f;
   }
   for (int r0 = 0; r0 < cnt; r0 += FR) {
-    for (int idx = tid; idx < S * N; idx += CT) {
-      const int s = idx >> a.log2n, n = idx & (N - 1);
+    load_frames<CT>(raw, stat, N, a.log2n, S, a.detrend, a.win, tid, [&](int s, int n) {
       const int p = s & (FR - 1);
       const float* src = (PAIR && s >= FR) ? yb : xb;
-      float v = 0.f;  // slots past the chunk's end stay zero and add nothing
-      if (r0 + p < cnt) v = src[(f0 + r0 + p) * a.hop + n];
-      if (a.detrend == SPECENH_DETREND_NONE) v *= a.win[n];
-      raw[idx] = v;
-    }
-    __syncthreads();
-    if (a.detrend != SPECENH_DETREND_NONE) {  // uniform; fp64 sums, one wave per slot
-      for (int s = tid >> 6; s < S; s += CT / 64) {
-        double sx = 0.0, skx = 0.0;
-        for (int n = tid & 63; n < N; n += 64) {
-          const double v = raw[s * N + n];
-          sx += v;
-          skx += ((double)n - 0.5 * (N - 1)) * v;
-        }
-        sx = wave_sum(sx);
-        skx = wave_sum(skx);
-        if ((tid & 63) == 0) {
-          const double skk = (double)N * ((double)N * N - 1.0) / 12.0;
-          stat[s][0] = (float)(sx / N);
-          stat[s][1] = a.detrend == SPECENH_DETREND_LINEAR ? (float)(skx / skk) : 0.f;
-        }
-      }
-      __syncthreads();
-      for (int idx = tid; idx < S * N; idx += CT) {
-        const int s = idx >> a.log2n, n = idx & (N - 1);
-        raw[idx] = (raw[idx] - stat[s][0] - stat[s][1] * ((float)n - kc)) * a.win[n];
-      }
-      __syncthreads();
-    }
-    const float2* res = fft_half<CT>(bufA, bufB, M, log2m, S, a.tw, tid);
+      // slots past the chunk's end stay zero and add nothing
+      return r0 + p < cnt ? src[(f0 + r0 + p) * a.hop + n] : 0.f;
+    });
+    const float2* res = stockham<CT>(bufA, bufB, M, log2m, S, a.tw, N, tid);
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
       const int idx = tid + CT * i, p = idx >> log2m, k = idx & (M - 1);
@@ -157,14 +127,14 @@ __global__ __launch_bounds__(CT) void spectral_mean_kernel(Args a) {
         acc[i][1] = fmaf(Y.x, Y.x, fmaf(Y.y, Y.y, acc[i][1]));
         acc[i][2] += fmaf(X.x, Y.x, X.y * Y.y);
         acc[i][3] += fmaf(X.x, Y.y, -X.y * Y.x);
-        if (k == 0) {  // 2 X_{N/2} = 2 (Re Z_0 - Im Z_0), real
-          const float xn = 2.f * (zx[0].x - zx[0].y), yn = 2.f * (zy[0].x - zy[0].y);
+        if (k == 0) {
+          const float xn = nyquist2(zx), yn = nyquist2(zy);
           accn[0] = fmaf(xn, xn, accn[0]);
           accn[1] = fmaf(yn, yn, accn[1]);
           accn[2] = fmaf(xn, yn, accn[2]);
         }
       } else if (k == 0) {
-        const float xn = 2.f * (zx[0].x - zx[0].y);
+        const float xn = nyquist2(zx);
         accn[0] = fmaf(xn, xn, accn[0]);
       }
     }
@@ -242,41 +212,14 @@ MeanKernel mean_kernel(int N, bool pair) {
        : N == 2048 ? spectral_mean_kernel<8, false> : spectral_mean_kernel<16, false>;
 }
 
-// N = 4096 takes 64 KiB of dynamic LDS next to the static stat[]: the attribute, once per
-// device and kernel
-hipError_t allow_lds() {
-  static bool done[64] = {};
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  if (dev >= 0 && dev < 64 && done[dev]) return hipSuccess;
-  for (int N = 1024; N <= 4096 && e == hipSuccess; N *= 2)
-    for (int pair = 0; pair < 2 && e == hipSuccess; ++pair)
-      e = hipFuncSetAttribute((const void*)mean_kernel(N, pair != 0),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS);
-  if (e == hipSuccess && dev >= 0 && dev < 64) done[dev] = true;
-  return e;
-}
-
-int ilog2i(int n) {
-  int l = 0;
-  while ((1 << l) < n) ++l;
-  return l;
-}
-
-// frames, groups, frames per group and chunks per group of a call, or a negative error
-struct Split {
-  long long T, G, glen, ncg;
-};
-int split_for(const specenh_stft_plan* plan, long long length, long long navg, Split* s) {
-  s->T = specenh_stft_frames(length, plan->nperseg, plan->noverlap);
-  if (s->T < 0) return (int)s->T;
-  s->G = specenh_spectral_groups(s->T, navg);
-  if (s->G < 0) return (int)s->G;
-  if (s->T > (1ll << 30)) return set_error(SPECENH_EINVAL, "too many frames");
-  s->glen = navg >= 1 ? navg : s->T;
-  s->ncg = (s->glen + CHUNK - 1) / CHUNK;
-  return SPECENH_OK;
+// N = 4096 takes 64 KiB of dynamic LDS next to the static stat[]: the attribute on every kernel
+LdsOptIn g_lds;
+hipError_t allow_mean_lds() {
+  return allow_lds(g_lds,
+                   {(const void*)mean_kernel(1024, false), (const void*)mean_kernel(1024, true),
+                    (const void*)mean_kernel(2048, false), (const void*)mean_kernel(2048, true),
+                    (const void*)mean_kernel(4096, false), (const void*)mean_kernel(4096, true)},
+                   MAX_LDS);
 }
 
 }  // namespace
@@ -295,12 +238,12 @@ long long specenh_spectral_groups(long long frames, long long navg) {
 size_t specenh_spectral_workspace_bytes(const specenh_stft_plan* plan, long long batch,
                                         long long length, long long navg) {
   using namespace specenh;
-  Split s;
+  FrameSplit s;
   if (!plan || batch < 0) {
     set_error(SPECENH_EINVAL, plan ? "batch must be >= 0" : "null plan");
     return 0;
   }
-  if (split_for(plan, length, navg, &s) != SPECENH_OK || s.ncg == 1) return 0;
+  if (frame_split(plan, length, navg, false, &s) != SPECENH_OK || s.ncg == 1) return 0;
   return (size_t)batch * s.G * s.ncg * (plan->nperseg / 2 + 1) * sizeof(float4);
 }
 
@@ -316,8 +259,8 @@ int specenh_spectral_mean(const specenh_stft_plan* plan, const float* x, const f
     return set_error(SPECENH_EINVAL, y && x_stride >= length ? "y_stride < length"
                                                              : "x_stride < length");
   const int N = plan->nperseg;
-  Split s;
-  const int rc = split_for(plan, length, navg, &s);
+  FrameSplit s;
+  const int rc = frame_split(plan, length, navg, false, &s);
   if (rc != SPECENH_OK) return rc;
   if (!y && (pyy || pxy || coh))
     return set_error(SPECENH_EINVAL, "pyy, pxy and coh need a second signal y");
@@ -329,7 +272,7 @@ int specenh_spectral_mean(const specenh_stft_plan* plan, const float* x, const f
     return set_error(SPECENH_EUNSUPPORTED, "too many groups");
   const long long F = N / 2 + 1;
   const bool pair = y != nullptr;
-  hipError_t e = allow_lds();
+  hipError_t e = allow_mean_lds();
   if (e != hipSuccess)
     return set_error(SPECENH_EHIP, std::string("spectral_mean: ") + hipGetErrorString(e));
   Args a{};

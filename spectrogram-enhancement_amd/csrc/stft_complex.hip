@@ -4,9 +4,10 @@
 // scipy.signal.istft semantics (scipy/signal/_spectral_py.py) for power-of-two nperseg in
 // [64, 4096], fp32 samples, complex64 spectra [batch][F][T] frequency-major, F = N/2 + 1.
 //
-// Both directions run a mixed-radix Stockham FFT (one radix-2 pass when log2 N is odd, then
-// radix-4) in LDS ping-pong buffers with the plan's natural-order twiddles W_N^n, P
-// transforms side by side per workgroup, and carry two real frames per complex transform:
+// Both directions run the mixed-radix Stockham FFT of fft_lds.hpp (one radix-2 pass when
+// log2 N is odd, then radix-4, in LDS ping-pong buffers) with the plan's natural-order
+// twiddles W_N^n, P transforms side by side per workgroup, and carry two real frames per
+// complex transform:
 //   forward  z = a + i b,  A_k = (Z_k + conj Z_{N-k}) / 2,  B_k = (Z_k - conj Z_{N-k}) / 2i;
 //   inverse  X = Afull + i Bfull over all N bins (Hermitian extensions),
 //            a + i b = conj(FFT(conj X)) / N  — the forward passes again.
@@ -32,11 +33,12 @@
 #include "specenh_stft_complex.h"
 #include "runtime.hpp"
 #include "stft_plan.hpp"
+#include "fft_lds.hpp"
 
 namespace specenh {
-int set_error(int code, const std::string& msg);  // stft_psd.hip
-
 namespace {
+
+using namespace fft_lds;  // wave_sum, stockham
 
 constexpr int CT = 256;            // threads per workgroup
 constexpr int SPT = 16;            // inverse: output samples per thread
@@ -61,63 +63,6 @@ inline Cfg cfg_for(int N) {
 }
 inline size_t fft_tile_bytes(int N, Cfg c) {
   return ((size_t)2 * c.P * N + (size_t)(N / 2 + 1) * (c.TF + 1)) * sizeof(float2);
-}
-
-__device__ __forceinline__ float2 c_mul(float2 a, float2 w) {
-  return make_float2(fmaf(a.x, w.x, -a.y * w.y), fmaf(a.x, w.y, a.y * w.x));
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
-
-// P forward FFTs of length N (transform p at [p * N, (p + 1) * N)), natural order in and
-// out. Returns the buffer that holds the result; ends on a barrier.
-__device__ __forceinline__ float2* fft_lds(float2* src, float2* dst, int N, int log2n, int P,
-                                           const float2* __restrict__ tw, int tid) {
-  const int total = P * N;
-  int Ns = 1;
-  if (log2n & 1) {
-    for (int idx = tid; idx < total / 2; idx += CT) {
-      const int base = (idx >> (log2n - 1)) << log2n, j = idx & (N / 2 - 1);
-      const float2 v0 = src[base + j], v1 = src[base + j + N / 2];
-      dst[base + 2 * j] = make_float2(v0.x + v1.x, v0.y + v1.y);
-      dst[base + 2 * j + 1] = make_float2(v0.x - v1.x, v0.y - v1.y);
-    }
-    float2* tmp = src; src = dst; dst = tmp;
-    Ns = 2;
-    __syncthreads();
-  }
-  const int q = N / 4;
-  for (; Ns < N; Ns *= 4) {
-    const int tstep = N / (4 * Ns);
-    for (int idx = tid; idx < total / 4; idx += CT) {
-      const int base = (idx >> (log2n - 2)) << log2n, j = idx & (q - 1);
-      const int jm = j & (Ns - 1);
-      const float2* s = src + base;
-      float2 v0 = s[j], v1 = s[j + q], v2 = s[j + 2 * q], v3 = s[j + 3 * q];
-      if (jm) {
-        const int e = jm * tstep;
-        v1 = c_mul(v1, tw[e]);
-        v2 = c_mul(v2, tw[2 * e]);
-        v3 = c_mul(v3, tw[3 * e]);  // 3 e < 3 N / 4
-      }
-      const float2 s02 = make_float2(v0.x + v2.x, v0.y + v2.y);
-      const float2 d02 = make_float2(v0.x - v2.x, v0.y - v2.y);
-      const float2 s13 = make_float2(v1.x + v3.x, v1.y + v3.y);
-      const float2 d13 = make_float2(v1.x - v3.x, v1.y - v3.y);  // -i * d13 = (d13.y, -d13.x)
-      float2* d = dst + base + (j - jm) * 4 + jm;
-      d[0] = make_float2(s02.x + s13.x, s02.y + s13.y);
-      d[Ns] = make_float2(d02.x + d13.y, d02.y - d13.x);
-      d[2 * Ns] = make_float2(s02.x - s13.x, s02.y - s13.y);
-      d[3 * Ns] = make_float2(d02.x - d13.y, d02.y + d13.x);
-    }
-    float2* tmp = src; src = dst; dst = tmp;
-    __syncthreads();
-  }
-  return src;
 }
 
 // ------------------------------------------------------------------------- forward
@@ -183,7 +128,7 @@ __global__ __launch_bounds__(CT) void stft_complex_kernel(FwdArgs a) {
       }
       __syncthreads();
     }
-    const float2* res = fft_lds(bufA, bufB, N, a.log2n, P, a.tw, tid);
+    const float2* res = stockham<CT>(bufA, bufB, N, a.log2n, P, a.tw, N, tid);
     for (int idx = tid; idx < P * F; idx += CT) {
       const int p = idx / F, k = idx - p * F;
       const float2 z = res[p * N + k], zc = res[p * N + ((N - k) & (N - 1))];
@@ -311,7 +256,7 @@ __global__ __launch_bounds__(CT) void istft_kernel(InvArgs a) {
                                : make_float2(A.x + B.y, A.y - B.x);
       }
       __syncthreads();
-      const float2* res = fft_lds(bufA, bufB, N, a.log2n, P, a.tw, tid);
+      const float2* res = stockham<CT>(bufA, bufB, N, a.log2n, P, a.tw, N, tid);
       // res[p N + n] = N (a_n - i b_n) of the frames tr + 2p (a) and tr + 2p + 1 (b)
 #pragma unroll
       for (int i = 0; i < SPT; ++i) {
@@ -348,26 +293,10 @@ __global__ __launch_bounds__(CT) void istft_kernel(InvArgs a) {
   }
 }
 
-// dynamic LDS above 64 KiB needs the attribute; once per device and kernel
-hipError_t allow_lds() {
-  static bool done[64] = {};
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  if (dev >= 0 && dev < 64 && done[dev]) return hipSuccess;
-  e = hipFuncSetAttribute((const void*)stft_complex_kernel,
-                          hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS);
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute((const void*)istft_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            MAX_LDS);
-  if (e == hipSuccess && dev >= 0 && dev < 64) done[dev] = true;
-  return e;
-}
-
-int ilog2i(int n) {
-  int l = 0;
-  while ((1 << l) < n) ++l;
-  return l;
+// dynamic LDS above 64 KiB needs the attribute on both kernels
+LdsOptIn g_lds;
+hipError_t allow_tile_lds() {
+  return allow_lds(g_lds, {(const void*)stft_complex_kernel, (const void*)istft_kernel}, MAX_LDS);
 }
 
 }  // namespace
@@ -414,7 +343,7 @@ int specenh_stft_complex(const specenh_stft_plan* plan, const float* x, long lon
   const Cfg c = cfg_for(N);
   const long long tiles = (T + c.TF - 1) / c.TF;
   if (tiles > 2147483647LL) return set_error(SPECENH_EUNSUPPORTED, "too many frames");
-  hipError_t e = allow_lds();
+  hipError_t e = allow_tile_lds();
   if (e != hipSuccess)
     return set_error(SPECENH_EHIP, std::string("stft_complex: ") + hipGetErrorString(e));
   FwdArgs a{};
@@ -456,7 +385,7 @@ int specenh_istft(const specenh_stft_plan* plan, const void* Z, const float* gai
   const long long spans = (n_out + SPAN - 1) / SPAN;
   if (frames > 2147483647LL - 64 || spans > 2147483647LL)
     return set_error(SPECENH_EUNSUPPORTED, "too many frames");
-  hipError_t e = allow_lds();
+  hipError_t e = allow_tile_lds();
   if (e != hipSuccess) return set_error(SPECENH_EHIP, std::string("istft: ") + hipGetErrorString(e));
   const Cfg c = cfg_for(N);
   InvArgs a{};

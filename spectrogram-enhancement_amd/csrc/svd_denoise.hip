@@ -32,7 +32,6 @@
 #include "runtime.hpp"
 
 namespace specenh {
-int set_error(int code, const std::string& msg);  // stft_psd.hip
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
