@@ -39,6 +39,7 @@
 
 #include "specenh.h"
 #include "runtime.hpp"
+#include "wave.hpp"
 
 namespace specenh {
 int launch_conv_narrow(int dtype, const void* in, int N, int IH, int IW, int C, const void* w,
@@ -65,13 +66,6 @@ template <>
 __device__ __forceinline__ __bf16 from_f<__bf16>(float x) { return (__bf16)x; }
 template <>
 __device__ __forceinline__ _Float16 from_f<_Float16>(float x) { return (_Float16)x; }
-
-// Barrier for LDS hand-off only: does not drain outstanding global loads (the prefetch).
-__device__ __forceinline__ void lds_sync() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 
 // ------------------------------------------------------------------ geometry
 // One dense implicit GEMM (one output phase):
@@ -388,14 +382,14 @@ __global__ __launch_bounds__(256) void conv_fwd_kernel(ConvArgs a) {
       const int co_l = idx / KG, kgb = idx - (idx / KG) * KG;
       if (idx < BG) st8(sB + co_l * LD + 8 * kgb, rb[j]);
     }
-    lds_sync();
+    lds_barrier();
     if (k0 + BK < K) fetch(k0 + BK);  // in flight during the MFMAs below
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
       for (int j = 0; j < NT; ++j)
         acc[i][j] = mfma_slab<T>(sA + 16 * (wave * MT + i) * LD, sB + 16 * j * LD, acc[i][j], lane);
-    lds_sync();
+    lds_barrier();
   }
 
   // epilogue: D[row][col], col = lane & 15, row = 4*(lane >> 4) + reg
@@ -456,11 +450,6 @@ struct Patch<1> { static constexpr int PST = 1; };
 // one VGPR for the whole k-loop and the k-step's column offset is a wave-uniform soffset, so
 // a weight-ring refill costs no VALU address arithmetic (and no temporaries whose reuse
 // would make the compiler drain the ring's other in-flight loads).
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t weight_rsrc(const void* base, long long bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0,
-                                           (int)(bytes < 0x7fffffffll ? bytes : 0x7fffffffll),
-                                           0x00020000);
-}
 template <typename T>
 __device__ __forceinline__ V8<T> ldw(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
   static_assert(sizeof(T) == 2, "16-bit weights");
@@ -549,7 +538,7 @@ void conv_patch_kernel(ConvArgs a) {
   // the per-tile program; K5 workgroups run it persistently over tiles blockIdx.x,
   // + gridDim.x, ... with the weight rows staged once (first)
   auto body = [&](const int bx_in, const bool first) {
-  if (!first) lds_sync();  // every wave is done with the previous tile's patch
+  if (!first) lds_barrier();  // every wave is done with the previous tile's patch
 
   // ---- phases of this workgroup: all of them over one shared patch, a row-phase pair
   // (PAIR), or blockIdx.z ----
@@ -700,7 +689,7 @@ void conv_patch_kernel(ConvArgs a) {
 
     for (int c = 0; c < nchunk; ++c) {
       if (p == ph_lo || nchunk > 1) {
-        if (c > 0 || p > ph_lo) lds_sync();  // previous chunk's fragment reads are done
+        if (c > 0 || p > ph_lo) lds_barrier();  // previous chunk's fragment reads are done
         stage(c);
         if constexpr (WL) {
           if (p == ph_lo && first) {  // this workgroup's 16 NT weight rows (all phases), once
@@ -722,7 +711,7 @@ void conv_patch_kernel(ConvArgs a) {
             }
           }
         }
-        lds_sync();
+        lds_barrier();
       }
       if constexpr (CC >= 32) {
         // ---- k-steps: one MFMA K=32 slab each; weights are the A operand (rows = output
@@ -736,7 +725,7 @@ void conv_patch_kernel(ConvArgs a) {
         const int dy = upt - g.pad_t, dx = upl - g.pad_l;  // this phase's shift in the patch
         const int kwinv = (65536 + KWl - 1) / KWl;         // t / KW == (t * kwinv) >> 16, t < 32
         const int nsteps = ntap * SUB;
-        const __amdgpu_buffer_rsrc_t wrs = weight_rsrc(W, (long long)g.CO * Kfl * sizeof(T));
+        const __amdgpu_buffer_rsrc_t wrs = buffer_rsrc(W, (long long)g.CO * Kfl * sizeof(T));
         int wv[NT];  // byte offset of this lane's weight row (+ chunk, k group)
 #pragma unroll
         for (int j = 0; j < NT; ++j)
@@ -812,7 +801,7 @@ void conv_patch_kernel(ConvArgs a) {
         const int kwinv = (65536 + KWl - 1) / KWl;
         const int nsteps = (ntap + 1) / 2;
         const bool second = (kgrp >> 1) != 0;
-        const __amdgpu_buffer_rsrc_t wrs = weight_rsrc(W, (long long)g.CO * Kfl * sizeof(T));
+        const __amdgpu_buffer_rsrc_t wrs = buffer_rsrc(W, (long long)g.CO * Kfl * sizeof(T));
         int wv[NT];
 #pragma unroll
         for (int j = 0; j < NT; ++j)
@@ -1130,7 +1119,7 @@ void conv_patch_kernel(ConvArgs a) {
         constexpr int CO = 16 * NT;  // the workgroup holds every channel (host-checked)
         constexpr int PS = 2 * CO + 8;  // a pixel pair + 16 B: spreads the lanes' 8-B writes
         constexpr int QV = 2 * CO / 8;  // 16-byte vectors per pixel pair
-        lds_sync();  // every wave's fragment reads of the patch are done
+        lds_barrier();  // every wave's fragment reads of the patch are done
 #pragma unroll
         for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -1139,7 +1128,7 @@ void conv_patch_kernel(ConvArgs a) {
             *reinterpret_cast<uint2*>(sP + o) = uint2{hold[i][j][0], hold[i][j][1]};
             *reinterpret_cast<uint2*>(sP + o + CO) = uint2{pk[i][j][0], pk[i][j][1]};
           }
-        lds_sync();
+        lds_barrier();
         T* __restrict__ out = reinterpret_cast<T*>(a.out);
         const int obase = ((n * g.OHs + pyp) * g.OWs + 2 * ox0) * CO;
         for (int e = tid; e < 16 * 16 * QV; e += 256) {
@@ -1345,7 +1334,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradArgs a) {
   if (p_begin < p_end) fetch(p_begin);
   for (int p0 = p_begin; p0 < p_end; p0 += BP) {
     stage();
-    lds_sync();
+    lds_barrier();
     if (p0 + BP < p_end) fetch(p0 + BP);
 #pragma unroll
     for (int j = 0; j < NT; ++j)
@@ -1354,7 +1343,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradArgs a) {
 #pragma unroll 8
       for (int p = 0; p < BP; ++p) bacc += to_f(sG[tid * LD + p]);
     }
-    lds_sync();
+    lds_barrier();
   }
 
   // D[co][k]: col = lane & 15 -> k, row = 4*(lane >> 4) + reg -> co
@@ -1629,7 +1618,7 @@ __global__ __launch_bounds__(256) void wgrad_tr_kernel(WgradTrArgs a) {
         const int e = tid + 256 * u;
         if (e < PH * PW) sIn[e] = rp1[u];
       }
-      lds_sync();
+      lds_barrier();
       // im2col row of this thread's pixel: taps (ky, kx) -> column ky*KW + kx; 31 = ones
       // (tap offsets from c1off, formed once: a run-time division per tap and tile had made
       // this kernel SALU-bound, 22 M SALU for 0.13 M MFMAs per C4 step)
@@ -1667,9 +1656,9 @@ __global__ __launch_bounds__(256) void wgrad_tr_kernel(WgradTrArgs a) {
 
   if (t_begin < t_end) fetch(t_begin);
   for (long long tile = t_begin; tile < t_end; ++tile) {
-    lds_sync();  // the previous tile's fragment reads are done
+    lds_barrier();  // the previous tile's fragment reads are done
     stage(tile);
-    lds_sync();
+    lds_barrier();
     if (tile + 1 < t_end) fetch(tile + 1);  // in flight while this tile computes
     if constexpr (C1) {
       // wave w: k-block kb = w & 1 (taps 16 kb .. 16 kb + 15), pixel groups of parity w >> 1
@@ -1729,14 +1718,14 @@ __global__ __launch_bounds__(256) void wgrad_tr_kernel(WgradTrArgs a) {
   if constexpr (C1) {
     // waves 2, 3 hand their sums to waves 0, 1 (same k-block): fixed-order pair sums
     float* red = reinterpret_cast<float*>(sD);
-    lds_sync();
+    lds_barrier();
     if (wave >= 2) {
 #pragma unroll
       for (int j = 0; j < NTW; ++j)
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) red[(((wave - 2) * NTW + j) * 4 + rr) * 64 + lane] = acc[0][j][rr];
     }
-    lds_sync();
+    lds_barrier();
     if (wave < 2) {
       const int t = 16 * wave + (lane & 15);
 #pragma unroll
@@ -1897,9 +1886,9 @@ __global__ __launch_bounds__(256) void wgrad_trp_kernel(WgradTrArgs a) {
 
   if (t_begin < t_end) fetch(t_begin);
   for (long long tile = t_begin; tile < t_end; ++tile) {
-    lds_sync();
+    lds_barrier();
     stage();
-    lds_sync();
+    lds_barrier();
     if (tile + 1 < t_end) fetch(tile + 1);
     // per pixel group: both dOut fragments and every B fragment read before the MFMAs, which
     // then run back to back (round 4 waited lgkmcnt(0) before each one and branched around
@@ -2026,7 +2015,7 @@ __global__ __launch_bounds__(64) void wgrad_co1_kernel(WgradTrArgs a) {
 
   if (t_begin < t_end) fetch(t_begin);
   for (long long tile = t_begin; tile < t_end; ++tile) {
-    lds_sync();  // the previous tile's fragment reads are done
+    lds_barrier();  // the previous tile's fragment reads are done
 #pragma unroll
     for (int u = 0; u < NPV; ++u) {
       const int e = lane + 64 * u;
@@ -2042,7 +2031,7 @@ __global__ __launch_bounds__(64) void wgrad_co1_kernel(WgradTrArgs a) {
         for (int s = 0; s < KW; ++s) sB[(s * 16 + row) * QC + c0 + k + s] = __builtin_bit_cast(T, b);
       }
     }
-    lds_sync();
+    lds_barrier();
     if (tile + 1 < t_end) fetch(tile + 1);
     // 12 chunks of 32 pixels: lane group g4 takes the 8-column run (row, cg) = pair 4 c + g4
 #pragma unroll 2

@@ -454,13 +454,9 @@ template <typename T, int C, int K>
 int launch_co1(const NarrowArgs& a, hipStream_t st) {
   using Rg = Co1Ring<C, K>;
   static_assert(Rg::LDS <= 160 * 1024, "LDS budget");
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)conv_co1_kernel<T, C, K>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, Rg::LDS) != hipSuccess)
-      return set_error(SPECENH_EHIP, "conv_co1 attribute");
-    attr = true;
-  }
+  static LdsOptIn lds_site;
+  if (allow_lds(lds_site, {(const void*)conv_co1_kernel<T, C, K>}, Rg::LDS) != hipSuccess)
+    return set_error(SPECENH_EHIP, "conv_co1 attribute");
   const long long strips = (long long)a.N * ((a.OW + Co1<C>::TW - 1) / Co1<C>::TW);
   // bands: ~1024 workgroups (every CU busy) unless the halo re-reads would exceed ~25%
   const int steps = (a.OH + Co1<C>::TR - 1) / Co1<C>::TR;

@@ -32,13 +32,13 @@
 
 #include <algorithm>
 #include <cstdint>
-#include <mutex>
 #include <string>
 #include <type_traits>
 
 #include "lds_dma.hpp"
 #include "specenh.h"
 #include "runtime.hpp"
+#include "wave.hpp"
 
 namespace specenh {
 
@@ -65,12 +65,6 @@ __device__ __forceinline__ uint32_t pack2(float lo, float hi) {
   typedef float f2 __attribute__((ext_vector_type(2)));
   typedef T t2 __attribute__((ext_vector_type(2)));
   return __builtin_bit_cast(uint32_t, __builtin_convertvector(f2{lo, hi}, t2));
-}
-
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
 }
 
 
@@ -1108,12 +1102,10 @@ template <typename T>
 hipError_t launch_convt_rows_pg(const CRArgs& a, hipStream_t st) {
   using C = TC<64, 16>;
   constexpr int LDS = 8 * C::RING * C::ROWB;
-  const void* k = reinterpret_cast<const void*>(&convt_rows_pg_kernel<T, 3>);
-  static bool attr[2] = {false, false};
-  if (!attr[__is_same(T, __bf16)]) {
-    (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    attr[__is_same(T, __bf16)] = true;
-  }
+  static LdsOptIn lds_site;
+  const hipError_t e =
+      allow_lds(lds_site, {reinterpret_cast<const void*>(&convt_rows_pg_kernel<T, 3>)}, LDS);
+  if (e != hipSuccess) return e;
   const long long grid = std::min<long long>(a.N, (long long)device_cus());
   SPECENH_LAUNCH((convt_rows_pg_kernel<T, 3>), dim3((unsigned)grid), dim3(512), LDS, st, a);
   return hipGetLastError();
@@ -1139,19 +1131,22 @@ hipError_t launch_convt_rows_pw(const CRArgs& a0, hipStream_t st) {
   constexpr int LDS = STORE8 ? 4 * C::RING * C::ROWB : C::LDS + 2 * CT_TILE;
   const void* k = STORE8 ? reinterpret_cast<const void*>(&convt_rows_pw_store8_kernel<T, 3>)
                          : reinterpret_cast<const void*>(&convt_rows_pw_kernel<T, 3>);
-  static int per_cu[64] = {};
+  static LdsOptIn lds_site;
+  static std::atomic<int> per_cu[64];  // resident workgroups per CU (0 = not queried)
+  hipError_t e = allow_lds(lds_site, {k}, LDS);
+  if (e != hipSuccess) return e;
   int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
+  e = hipGetDevice(&dev);
   if (e != hipSuccess) return e;
   if (dev < 0 || dev >= 64) dev = 0;
-  if (per_cu[dev] == 0) {
-    (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    int pc = 0;
+  int pc = per_cu[dev].load(std::memory_order_relaxed);
+  if (pc == 0) {
     e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, k, 256, LDS);
     if (e != hipSuccess) return e;
-    per_cu[dev] = std::max(1, pc);
+    pc = std::max(1, pc);
+    per_cu[dev].store(pc, std::memory_order_relaxed);  // same value from any racing thread
   }
-  const long long slots = (long long)per_cu[dev] * device_cus();
+  const long long slots = (long long)pc * device_cus();
   CRArgs a = a0;
   a.lgb = convt_row_bands_lg(a.N, a.H, slots);
   const long long grid = std::min<long long>((long long)a.N << a.lgb, slots);
@@ -2058,15 +2053,13 @@ extern "C" int specenh_encoder2(int dtype, const void* x, int N, int H, int W, c
   E2Args a{};
   a.x = x; a.w1 = w1_gemm; a.b1 = b1; a.w2 = w2_gemm; a.b2 = b2; a.out = out; a.N = N; a.H = H;
   hipStream_t st = (hipStream_t)stream;
-  static std::once_flag once;
-  std::call_once(once, [] {
-    const void* const ks[4] = {reinterpret_cast<const void*>(&enc2_rows_kernel<_Float16, 4>),
-                               reinterpret_cast<const void*>(&enc2_rows_kernel<__bf16, 4>),
-                               reinterpret_cast<const void*>(&enc2_rows_kernel<_Float16, 2>),
-                               reinterpret_cast<const void*>(&enc2_rows_kernel<__bf16, 2>)};
-    for (const void* k : ks)
-      (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, E2LDS);
-  });
+  static LdsOptIn lds_site;
+  (void)allow_lds(lds_site,
+                  {reinterpret_cast<const void*>(&enc2_rows_kernel<_Float16, 4>),
+                   reinterpret_cast<const void*>(&enc2_rows_kernel<__bf16, 4>),
+                   reinterpret_cast<const void*>(&enc2_rows_kernel<_Float16, 2>),
+                   reinterpret_cast<const void*>(&enc2_rows_kernel<__bf16, 2>)},
+                  E2LDS);
   const hipError_t e = dtype == SPECENH_DTYPE_F16 ? launch_enc2<_Float16>(a, st)
                                                   : launch_enc2<__bf16>(a, st);
   if (e != hipSuccess) return set_error(SPECENH_EHIP, std::string("encoder2: ") + hipGetErrorString(e));

@@ -63,7 +63,7 @@ struct CsdArgs {
   void* out;  // mode 0: float2 [B][F][T]; mode 1: float |Pxy| [B][F][T]
 };
 
-using namespace fft_lds;  // wave_sum, stockham
+using namespace fft_lds;  // stockham
 
 __global__ __launch_bounds__(CT) void csd_kernel(CsdArgs a) {
   extern __shared__ float2 sm[];  // 2 x N complex

@@ -31,7 +31,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <mutex>
 #include <cstdlib>
 #include <cstdint>
 #include <string>
@@ -41,6 +40,7 @@
 #include "lds_dma.hpp"
 #include "specenh.h"
 #include "runtime.hpp"
+#include "wave.hpp"
 
 namespace specenh {
 
@@ -103,12 +103,6 @@ __device__ __forceinline__ uint32_t pack2(float lo, float hi) {
   const T a = (T)lo, b = (T)hi;
   return (uint32_t)__builtin_bit_cast(unsigned short, a) |
          ((uint32_t)__builtin_bit_cast(unsigned short, b) << 16);
-}
-
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
 }
 
 // Phase PH = py * 2 + px: its taps in (dy, dx) order, compile-time (static register indices).
@@ -1422,26 +1416,21 @@ extern "C" int specenh_decoder3_ex(int dtype, const void* x, int N, int H, int W
   a.out = out; a.N = N; a.H = H;
   a.out_f16 = out_dtype == SPECENH_DTYPE_F16;
   hipStream_t st = (hipStream_t)stream;
-  // (the kernels are named here, outside the lambda, so the device compilation instantiates
-  // them)
-  const void* const k16 = reinterpret_cast<const void*>(&decoder3_kernel<_Float16, true, 0>);
-  const void* const kb16 = reinterpret_cast<const void*>(&decoder3_kernel<__bf16, true, 0>);
-  static std::once_flag attr_once;
-  std::call_once(attr_once, [k16, kb16] {
-    (void)hipFuncSetAttribute(k16, hipFuncAttributeMaxDynamicSharedMemorySize, d3::LDS_BYTES);
-    (void)hipFuncSetAttribute(kb16, hipFuncAttributeMaxDynamicSharedMemorySize, d3::LDS_BYTES);
-    const void* const nm[8] = {
-        reinterpret_cast<const void*>(&decoder3_kernel<_Float16, false, 3>),
-        reinterpret_cast<const void*>(&decoder3_kernel<__bf16, false, 3>),
-        reinterpret_cast<const void*>(&decoder3_kernel<_Float16, false, 0>),
-        reinterpret_cast<const void*>(&decoder3_kernel<__bf16, false, 0>),
-        reinterpret_cast<const void*>(&decoder3_kernel<_Float16, false, 3, true>),
-        reinterpret_cast<const void*>(&decoder3_kernel<__bf16, false, 3, true>),
-        reinterpret_cast<const void*>(&decoder3_kernel<_Float16, false, 0, true>),
-        reinterpret_cast<const void*>(&decoder3_kernel<__bf16, false, 0, true>)};
-    for (const void* k : nm)
-      (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, d3::LDS_BYTES_NM);
-  });
+  static LdsOptIn lds_map, lds_nm;  // with and without the map ring
+  (void)allow_lds(lds_map,
+                  {reinterpret_cast<const void*>(&decoder3_kernel<_Float16, true, 0>),
+                   reinterpret_cast<const void*>(&decoder3_kernel<__bf16, true, 0>)},
+                  d3::LDS_BYTES);
+  (void)allow_lds(lds_nm,
+                  {reinterpret_cast<const void*>(&decoder3_kernel<_Float16, false, 3>),
+                   reinterpret_cast<const void*>(&decoder3_kernel<__bf16, false, 3>),
+                   reinterpret_cast<const void*>(&decoder3_kernel<_Float16, false, 0>),
+                   reinterpret_cast<const void*>(&decoder3_kernel<__bf16, false, 0>),
+                   reinterpret_cast<const void*>(&decoder3_kernel<_Float16, false, 3, true>),
+                   reinterpret_cast<const void*>(&decoder3_kernel<__bf16, false, 3, true>),
+                   reinterpret_cast<const void*>(&decoder3_kernel<_Float16, false, 0, true>),
+                   reinterpret_cast<const void*>(&decoder3_kernel<__bf16, false, 0, true>)},
+                  d3::LDS_BYTES_NM);
   // persistent: one workgroup per CU (256 VGPRs at 2 waves per SIMD; 68 KB of LDS, 120 KB with
   // the map ring)
   const unsigned grid = (unsigned)std::min<long long>(N, device_cus());

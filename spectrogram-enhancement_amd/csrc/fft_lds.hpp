@@ -9,18 +9,13 @@
 #include <hip/hip_runtime.h>
 
 #include "specenh.h"
+#include "wave.hpp"  // wave_sum
 
 namespace specenh {
 namespace fft_lds {
 
 __device__ __forceinline__ float2 c_mul(float2 a, float2 w) {
   return make_float2(fmaf(a.x, w.x, -a.y * w.y), fmaf(a.x, w.y, a.y * w.x));
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  return v;
 }
 
 // P forward FFTs of length Lf (transform p at [p * Lf, (p + 1) * Lf)), natural order in and

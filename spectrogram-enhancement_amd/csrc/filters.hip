@@ -18,24 +18,11 @@
 
 #include "specenh.h"
 #include "runtime.hpp"
+#include "wave.hpp"
 
 namespace specenh {
 
 namespace {
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
-
-__device__ double block_sum(double v, double* red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 __device__ void block_minmax(double& mn, double& mx, double* red) {
 #pragma unroll
@@ -81,13 +68,13 @@ __global__ __launch_bounds__(256) void stats_kernel(const T* S, int rows, int co
   if (op == SPECENH_FILTER_NORM) {
     double acc = 0.0;
     for (long long e = threadIdx.x; e < n; e += 256) acc += (double)s[e];
-    const double mean = block_sum(acc, red) / (double)n;
+    const double mean = block_sum256(acc, red) / (double)n;
     double a2 = 0.0;
     for (long long e = threadIdx.x; e < n; e += 256) {
       const double d = (double)s[e] - mean;
       a2 += d * d;
     }
-    const double var = block_sum(a2, red) / (double)n;
+    const double var = block_sum256(a2, red) / (double)n;
     if (threadIdx.x == 0) {
       stats[2 * b] = mean;
       stats[2 * b + 1] = sqrt(var);
@@ -134,6 +121,7 @@ __global__ __launch_bounds__(256) void apply_kernel(const T* S, T* out, long lon
 }
 
 constexpr int QF_COLS = 16;  // columns per workgroup
+constexpr int QF_MAX_LDS = 160 * 1024 - 512;  // largest column block (dynamic LDS) accepted
 
 // quantfilt: order statistics lo/hi of each column by stable rank counting, numpy's lerp,
 // threshold. Columns of the tile live column-major in LDS.
@@ -325,8 +313,8 @@ template <typename T>
 int run_quantfilt(const T* S, long long batch, int rows, int cols, long long stride, int lo,
                   int hi, double gamma, T* out, hipStream_t st) {
   const size_t lds = (size_t)rows * QF_COLS * sizeof(T);
-  if (hipFuncSetAttribute((const void*)quantfilt_kernel<T>,
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+  static LdsOptIn lds_site;
+  if (allow_lds(lds_site, {(const void*)quantfilt_kernel<T>}, QF_MAX_LDS) != hipSuccess)
     return set_error(SPECENH_EHIP, "quantfilt attribute");
   for (long long b0 = 0; b0 < batch; b0 += 65535) {
     const long long nb = std::min<long long>(65535, batch - b0);
@@ -474,7 +462,7 @@ int specenh_quantfilt(int dtype, const void* S, long long batch, int rows, int c
                       long long stride, double thr, void* out, void* stream) {
   if (int e = check_common(dtype, S, batch, rows, cols, stride, out)) return e;
   if (!(thr >= 0.0 && thr <= 1.0)) return set_error(SPECENH_EINVAL, "Quantiles must be in the range [0, 1]");
-  if ((size_t)rows * QF_COLS * (dtype == SPECENH_DTYPE_F64 ? 8 : 4) > 160 * 1024 - 512)
+  if ((size_t)rows * QF_COLS * (dtype == SPECENH_DTYPE_F64 ? 8 : 4) > QF_MAX_LDS)
     return set_error(SPECENH_EUNSUPPORTED, "quantfilt on the GPU needs rows <= 1264");
   if (batch == 0) return SPECENH_OK;
   // numpy 'linear' (alpha = beta = 1): virtual index, neighbours, gamma (_quantile)

@@ -1,6 +1,8 @@
-// runtime.hip — variant switches, per-device CU counts, last-launch record (runtime.hpp).
+// runtime.hip — error record, variant switches, per-device CU counts, LDS opt-in, last-launch
+// record (runtime.hpp).
 #include "runtime.hpp"
 
+#include <algorithm>
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
@@ -58,7 +60,14 @@ constexpr int kRing = 256;  // the calling thread's last kRing launches
 thread_local const void* g_ring[kRing];
 thread_local long long g_launches = 0;
 
+thread_local std::string g_last_error;
+
 }  // namespace
+
+int set_error(int code, const std::string& msg) {
+  g_last_error = msg;
+  return code;
+}
 
 int variant(Variant v) {
   std::call_once(g_variant_once, init_variants);
@@ -84,7 +93,13 @@ hipError_t allow_lds(LdsOptIn& site, std::initializer_list<const void*> kernels,
   const bool known = dev >= 0 && dev < kMaxDevices;
   if (known && site.done[dev].load(std::memory_order_acquire)) return hipSuccess;
   for (const void* k : kernels) {
-    e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    // the runtime refuses static + dynamic LDS above the CU's 160 KiB: a caller's upper bound
+    // is cut to what the kernel's static LDS leaves
+    hipFuncAttributes fa{};
+    e = hipFuncGetAttributes(&fa, k);
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            std::min(bytes, 160 * 1024 - (int)fa.sharedSizeBytes));
     if (e != hipSuccess) return e;
   }
   if (known) site.done[dev].store(true, std::memory_order_release);  // racing threads set the same
@@ -96,6 +111,8 @@ void note_launch(const void* kernel) { g_ring[g_launches++ % kRing] = kernel; }
 }  // namespace specenh
 
 extern "C" {
+
+const char* specenh_last_error(void) { return specenh::g_last_error.c_str(); }
 
 int specenh_set_variant(const char* name, int value) {
   const int i = specenh::variant_index(name);

@@ -16,7 +16,7 @@
 
 namespace specenh {
 
-// record `msg` as the calling thread's last error and return `code` (stft_psd.hip)
+// record `msg` as the calling thread's last error (specenh_last_error) and return `code`
 int set_error(int code, const std::string& msg);
 
 // log2 of a power of two (rounded up otherwise)
@@ -78,6 +78,8 @@ int device_cus();
 // Dynamic LDS above the default needs an attribute on each kernel: set it to `bytes` for
 // `kernels` on the calling thread's device, once per device and call site (`site`: the call
 // site's flags, a zero-initialised static). A later call is one hipGetDevice and one load.
+// `bytes` may be an upper bound of what the launches ask for: it is cut to what a kernel's
+// static LDS leaves of the CU's 160 KiB, which is the most the runtime accepts.
 struct LdsOptIn {
   std::atomic<bool> done[64];
 };

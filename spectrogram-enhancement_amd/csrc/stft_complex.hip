@@ -38,7 +38,7 @@
 namespace specenh {
 namespace {
 
-using namespace fft_lds;  // wave_sum, stockham
+using namespace fft_lds;  // stockham
 
 constexpr int CT = 256;            // threads per workgroup
 constexpr int SPT = 16;            // inverse: output samples per thread

@@ -58,6 +58,8 @@
 #endif
 #include "specenh.h"
 #include "runtime.hpp"
+#include "stft_plan.hpp"
+#include "wave.hpp"
 
 // Development-only flag bit (not part of the public header): skip the output store,
 // to separate compute from store cost when profiling.
@@ -66,13 +68,6 @@
 #define SPECENH_STFT_DEV_NOLOAD (1 << 21)
 
 namespace specenh {
-
-thread_local std::string g_last_error;
-
-int set_error(int code, const std::string& msg) {
-  g_last_error = msg;
-  return code;
-}
 
 #define SPECENH_HIP_CHECK(expr)                                                          \
   do {                                                                                   \
@@ -212,44 +207,17 @@ __device__ __forceinline__ float fmax3(float a, float b, float c) {
   return r;
 }
 
-// Workgroup barrier that orders LDS only: waits for this wave's LDS ops (lgkmcnt) and
-// meets the other waves, but leaves global loads (the register prefetch) and global
-// stores in flight. __syncthreads() would add s_waitcnt vmcnt(0) and serialise both.
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-
 // ---------------------------------------------------------------- lane-group sums
 // Sum over aligned groups of G lanes, result in every lane of the group. DPP
 // (quad_perm, row half-mirror, row mirror) inside a 16-lane row; ds_swizzle / a
 // 32-lane shuffle above that.
-template <int CTRL>
-__device__ __forceinline__ float dppf(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-template <int CTRL>
-__device__ __forceinline__ double dppd(double v) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)b, CTRL, 0xF, 0xF, true);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xF, 0xF, true);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
 template <int G, typename T>
 __device__ __forceinline__ T group_sum(T v) {
   static_assert(G >= 4 && G <= 64, "group size");
-  if constexpr (sizeof(T) == 4) {
-    v += dppf<0xB1>(v);  // quad_perm [1,0,3,2]
-    v += dppf<0x4E>(v);  // quad_perm [2,3,0,1]
-    if constexpr (G >= 8) v += dppf<0x141>(v);   // row_half_mirror
-    if constexpr (G >= 16) v += dppf<0x140>(v);  // row_mirror
-  } else {
-    v += dppd<0xB1>(v);
-    v += dppd<0x4E>(v);
-    if constexpr (G >= 8) v += dppd<0x141>(v);
-    if constexpr (G >= 16) v += dppd<0x140>(v);
-  }
+  v += dpp<0xB1, true>(v);  // quad_perm [1,0,3,2]
+  v += dpp<0x4E, true>(v);  // quad_perm [2,3,0,1]
+  if constexpr (G >= 8) v += dpp<0x141, true>(v);   // row_half_mirror
+  if constexpr (G >= 16) v += dpp<0x140, true>(v);  // row_mirror
   if constexpr (G >= 32) v += __shfl_xor(v, 16);
   if constexpr (G >= 64) v += __shfl_xor(v, 32);
   return v;
@@ -318,14 +286,6 @@ struct PairSamples {
   static constexpr int BPL1 = (N / R1) / Cfg<N>::G;
   f2v x[BPL1][R1];  // {frame a, frame b} sample pairs
 };
-
-// Shot-local buffer descriptor (wave-uniform base, 32-bit offsets): every sample load
-// and row store is then one VGPR offset + an immediate, not a 64-bit address pair.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, long long bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0,
-                                           (int)(bytes < 0x7fffffffll ? bytes : 0x7fffffffll),
-                                           0x00020000);
-}
 
 // XH: the samples are fp16 (the C5 stream's shots), widened to fp32 on load (exact).
 // XY: the pair is frame fa of two signals (x from xr, y from yr: the cross spectrum);
@@ -828,7 +788,7 @@ __global__ __launch_bounds__(Layout<N>::THREADS, Layout<N>::WPE) void stft_psd_k
   const int fi = wave * (64 / G) + lane / G;        // FFT index within the tile
   float* buf = reinterpret_cast<float*>(smem + Lo::OFF_BUF) + fi * Lo::BUF;
   constexpr int ES = XH ? 2 : 4;
-  const __amdgpu_buffer_rsrc_t xr = make_rsrc(
+  const __amdgpu_buffer_rsrc_t xr = buffer_rsrc(
       reinterpret_cast<const char*>(a.x) + shot * a.x_stride * ES, a.x_stride * ES);
   const bool want_log = (a.flags & (SPECENH_STFT_LOG | SPECENH_STFT_NORMALIZE)) != 0;
   const bool log2_out = (a.flags & SPECENH_STFT_NORMALIZE) != 0;
@@ -837,9 +797,9 @@ __global__ __launch_bounds__(Layout<N>::THREADS, Layout<N>::WPE) void stft_psd_k
   float lmin = INFINITY, lmax = -INFINITY;
   const double dcb = dc_lane_base<N>(a, gl);
 
-  const __amdgpu_buffer_rsrc_t orr = make_rsrc(o_shot, (long long)a.F_out * a.T * 4);
+  const __amdgpu_buffer_rsrc_t orr = buffer_rsrc(o_shot, (long long)a.F_out * a.T * 4);
   PairSamples<N> s0;
-  const __amdgpu_buffer_rsrc_t zr = make_rsrc(a.x, 0);  // EXACT: the zero partner frame
+  const __amdgpu_buffer_rsrc_t zr = buffer_rsrc(a.x, 0);  // EXACT: the zero partner frame
   if constexpr (EXACT) {
     if constexpr (C::PF) load_pair<N, XH, true>(s0, xr, zr, a.hop, 2 * fi, a.T, gl);
   } else if constexpr (C::PF) {
@@ -956,20 +916,18 @@ __global__ __launch_bounds__(Layout<N>::THREADS, Layout<N>::WPE) void stft_psd_k
 template <int N, bool XH = false>
 hipError_t launch_stft(const StftArgs& a, long long batch, hipStream_t stream) {
   using Lo = Layout<N>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)stft_psd_kernel<N, XH>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, Lo::BYTES);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)stft_psd_kernel<N, XH, 0, true>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, Lo::BYTES);
-    if constexpr (N <= 512)
-      for (const void* k : {(const void*)stft_psd_kernel<N, XH, 1>, (const void*)stft_psd_kernel<N, XH, 2>})
-        if (e == hipSuccess)
-          e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, Lo::BYTES);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
+  static LdsOptIn lds_site;
+  hipError_t e;
+  if constexpr (N <= 512)
+    e = allow_lds(lds_site,
+                  {(const void*)stft_psd_kernel<N, XH>, (const void*)stft_psd_kernel<N, XH, 0, true>,
+                   (const void*)stft_psd_kernel<N, XH, 1>, (const void*)stft_psd_kernel<N, XH, 2>},
+                  Lo::BYTES);
+  else
+    e = allow_lds(lds_site,
+                  {(const void*)stft_psd_kernel<N, XH>, (const void*)stft_psd_kernel<N, XH, 0, true>},
+                  Lo::BYTES);
+  if (e != hipSuccess) return e;
   if (a.flags & SPECENH_STFT_EXACT) {
     SPECENH_LAUNCH((stft_psd_kernel<N, XH, 0, true>), dim3((unsigned)batch), dim3(Lo::THREADS),
                    Lo::BYTES, stream, a);
@@ -1121,8 +1079,8 @@ __global__ __launch_bounds__(Layout<N>::THREADS, Layout<N>::WPE) void stft_team_
     const int t1 = mem * Tile1<N>::TF1;
     const int f1 = t1 + fi;
     const long long ybytes = a.y_stride * 4;
-    load_pair<N, false, true>(s0, make_rsrc(a.x + q * a.x_stride, xbytes),
-                              make_rsrc(a.y + q * a.y_stride, ybytes), a.hop, f1, a.T, gl);
+    load_pair<N, false, true>(s0, buffer_rsrc(a.x + q * a.x_stride, xbytes),
+                              buffer_rsrc(a.y + q * a.y_stride, ybytes), a.hop, f1, a.T, gl);
     __syncthreads();
     for (long long it = 0; it < ntask; ++it) {
       const long long shot = q + it * Q;
@@ -1130,20 +1088,20 @@ __global__ __launch_bounds__(Layout<N>::THREADS, Layout<N>::WPE) void stft_team_
       float dmin = INFINITY, dmax = -INFINITY;  // (pair_spectrum's running extremes: unused)
       f2v pv[IB];
       pair_spectrum<N, false, true>(a, s0, s0, s_tw, s_win, s_dc, buf, gl, dcb,
-                                    make_rsrc(a.x + nshot * a.x_stride, xbytes),
-                                    make_rsrc(a.y + nshot * a.y_stride, ybytes), f1, true, false,
+                                    buffer_rsrc(a.x + nshot * a.x_stride, xbytes),
+                                    buffer_rsrc(a.y + nshot * a.y_stride, ybytes), f1, true, false,
                                     false, pv, dmin, dmax);
       float amp[IB];
 #pragma unroll
       for (int i = 0; i < IB; ++i) amp[i] = __builtin_sqrtf(pv[i].x) * __builtin_sqrtf(pv[i].y);
-      tile_store1<N>(a, s_tile, amp, gl, fi, tid, make_rsrc(a.out + shot * plane, plane * 4), t1);
+      tile_store1<N>(a, s_tile, amp, gl, fi, tid, buffer_rsrc(a.out + shot * plane, plane * 4), t1);
     }
     return;
   }
   // C::PF = 0: no register prefetch; each task loads its own samples at its start (the
   // other resident waves cover the latency)
   if constexpr (C::PF)
-    load_pair<N>(s0, make_rsrc(a.x + q * a.x_stride, xbytes), make_rsrc(a.x, 0), a.hop, fa, a.T, gl);
+    load_pair<N>(s0, buffer_rsrc(a.x + q * a.x_stride, xbytes), buffer_rsrc(a.x, 0), a.hop, fa, a.T, gl);
   __syncthreads();
 
   // Per task: the tile's spectrum (next task's samples prefetched meanwhile), publish the
@@ -1153,7 +1111,7 @@ __global__ __launch_bounds__(Layout<N>::THREADS, Layout<N>::WPE) void stft_team_
   for (long long it = 0; it < ntask; ++it) {
     const long long shot = q + it * Q;
     const bool pf = it + 1 < ntask;
-    const __amdgpu_buffer_rsrc_t xn = make_rsrc(a.x + (pf ? shot + Q : shot) * a.x_stride, xbytes);
+    const __amdgpu_buffer_rsrc_t xn = buffer_rsrc(a.x + (pf ? shot + Q : shot) * a.x_stride, xbytes);
     f2v pv[IB];
     float dmin = INFINITY, dmax = -INFINITY;  // (pair_spectrum's running extremes: unused)
     // NORMALIZE: the next task's samples are requested after the team wait, not inside
@@ -1161,11 +1119,11 @@ __global__ __launch_bounds__(Layout<N>::THREADS, Layout<N>::WPE) void stft_team_
     // first wait for its whole prefetch to land while the workgroup idles at the barrier
     constexpr bool pf_inside = C::PF && (!normalize || !SPECENH_STFT_PF_AFTER_WAIT);
     if constexpr (!C::PF)
-      load_pair<N>(s0, make_rsrc(a.x + shot * a.x_stride, xbytes), make_rsrc(a.x, 0), a.hop, fa, a.T,
+      load_pair<N>(s0, buffer_rsrc(a.x + shot * a.x_stride, xbytes), buffer_rsrc(a.x, 0), a.hop, fa, a.T,
                    gl);
     pair_spectrum<N>(a, s0, s0, s_tw, s_win, s_dc, buf, gl, dcb, xn, xn, fa, pf_inside, want_log, normalize,
                      pv, dmin, dmax);
-    const __amdgpu_buffer_rsrc_t orr = make_rsrc(a.out + shot * plane, plane * 4);
+    const __amdgpu_buffer_rsrc_t orr = buffer_rsrc(a.out + shot * plane, plane * 4);
     if constexpr (!normalize) {
       tile_store<N>(a, s_tile, pv, gl, fi, tid, orr, t0, 0.f, 1.f, false);
       continue;
@@ -1270,15 +1228,16 @@ hipError_t launch_team_mode(const StftArgs& a, long long batch, void* workspace,
   const int TFM = MODE == 3 ? Tile1<N>::TF1 : Lo::TF;  // frames per member tile
   const int M = (a.T + TFM - 1) / TFM;
   if (M > TEAM_MAX) return hipSuccess;
-  static int cap[64] = {};  // resident workgroups per device (0 = not queried)
+  static LdsOptIn lds_site;
+  static std::atomic<int> caps[64];  // resident workgroups per device (0 = not queried)
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
   if (e != hipSuccess) return e;
   if (dev < 0 || dev >= 64) return hipSuccess;
-  if (cap[dev] == 0) {
-    e = hipFuncSetAttribute((const void*)stft_team_kernel<N, MODE>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, Lo::BYTES);
-    if (e != hipSuccess) return e;
+  e = allow_lds(lds_site, {(const void*)stft_team_kernel<N, MODE>}, Lo::BYTES);
+  if (e != hipSuccess) return e;
+  int cap = caps[dev].load(std::memory_order_relaxed);
+  if (cap == 0) {
     int per_cu = 0, cus = 0;
     e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)stft_team_kernel<N, MODE>,
                                                      Lo::THREADS, Lo::BYTES);
@@ -1296,10 +1255,11 @@ hipError_t launch_team_mode(const StftArgs& a, long long batch, void* workspace,
     const int by_regs = waves_per_simd * 4 / Cfg<N>::WAVES;
     const int by_lds = (160 * 1024) / Lo::BYTES;
     per_cu = std::min(per_cu, std::min(by_regs, by_lds));
-    cap[dev] = per_cu * cus > 0 ? per_cu * cus : -1;
+    cap = per_cu * cus > 0 ? per_cu * cus : -1;
+    caps[dev].store(cap, std::memory_order_relaxed);  // same value from any racing thread
   }
-  if (cap[dev] < M) return hipSuccess;
-  long long Q = cap[dev] / M;
+  if (cap < M) return hipSuccess;
+  long long Q = cap / M;
   if (Q > batch) Q = batch;
   const int xcd_teams = Q >= 8;
   if (xcd_teams) Q &= ~7ll;  // Q / 8 teams per XCD
@@ -1344,8 +1304,6 @@ hipError_t launch_team(const StftArgs& a, long long batch, void* workspace, hipS
 
 using namespace specenh;
 
-#include "stft_plan.hpp"
-
 namespace specenh {
 // Cross-spectrum amplitude |Pxy| [batch][N/2 + 1][T] of the signal pairs (x[b], y[b]) on the
 // team schedule (stft_team_kernel MODE 3), with the tables of an STFT plan of the same
@@ -1354,12 +1312,51 @@ namespace specenh {
 // caller (specenh_csd) then runs csd_kernel.
 int stft_csd_amplitude(const specenh_stft_plan* plan, const float* x, const float* y,
                        long long batch, long long length, long long x_stride, long long y_stride,
-                       float* out, hipStream_t stream, bool* launched);
+                       float* out, hipStream_t stream, bool* launched) {
+  *launched = false;
+  const int N = plan->nperseg;
+  const long long T = specenh_stft_frames(length, N, plan->noverlap);
+  if (T < 0) return (int)T;
+  if (N > 1024 || batch > (1ll << 30) || (long long)(N / 2 + 1) * T * 4 >= (1ll << 30) ||
+      x_stride * 4 >= (1ll << 31) || y_stride * 4 >= (1ll << 31))
+    return SPECENH_OK;
+  StftArgs a{};
+  a.x = x;
+  a.x_stride = x_stride;
+  a.y = y;
+  a.y_stride = y_stride;
+  a.T = (int)T;
+  a.hop = plan->hop;
+  a.scale = (float)plan->scale;
+  a.eps = 0.f;
+  a.inv_kk = (float)(12.0 / ((double)N * ((double)N * N - 1.0)));
+  a.detrend = plan->detrend;
+  a.flags = 0;
+  a.out = out;
+  a.F_out = N / 2 + 1;
+  a.window = plan->d_window;
+  a.twiddle = plan->d_twiddle;
+  a.dc_alpha = plan->dc_alpha;
+  a.dc_beta = plan->dc_beta;
+  a.dc_coef = plan->d_dc;
+  hipError_t e = hipSuccess;
+  switch (N) {
+    case 64: e = launch_team_mode<64, 3>(a, batch, nullptr, stream, launched); break;
+    case 128: e = launch_team_mode<128, 3>(a, batch, nullptr, stream, launched); break;
+    case 256: e = launch_team_mode<256, 3>(a, batch, nullptr, stream, launched); break;
+    case 512: e = launch_team_mode<512, 3>(a, batch, nullptr, stream, launched); break;
+    case 1024: e = launch_team_mode<1024, 3>(a, batch, nullptr, stream, launched); break;
+    default: break;
+  }
+  if (e != hipSuccess)
+    return set_error(SPECENH_EHIP, std::string("csd team launch: ") + hipGetErrorString(e));
+  return SPECENH_OK;
+}
+
 }  // namespace specenh
 
 extern "C" {
 
-const char* specenh_last_error(void) { return g_last_error.c_str(); }
 const char* specenh_version(void) { return "specenh 0.1.0 gfx950"; }
 
 long long specenh_stft_frames(long long length, int nperseg, int noverlap) {
@@ -1617,50 +1614,3 @@ int specenh_stft_psd_f16(const specenh_stft_plan* plan, const void* x, long long
 }
 
 }  // extern "C"
-
-namespace specenh {
-
-int stft_csd_amplitude(const specenh_stft_plan* plan, const float* x, const float* y,
-                       long long batch, long long length, long long x_stride, long long y_stride,
-                       float* out, hipStream_t stream, bool* launched) {
-  *launched = false;
-  const int N = plan->nperseg;
-  const long long T = specenh_stft_frames(length, N, plan->noverlap);
-  if (T < 0) return (int)T;
-  if (N > 1024 || batch > (1ll << 30) || (long long)(N / 2 + 1) * T * 4 >= (1ll << 30) ||
-      x_stride * 4 >= (1ll << 31) || y_stride * 4 >= (1ll << 31))
-    return SPECENH_OK;
-  StftArgs a{};
-  a.x = x;
-  a.x_stride = x_stride;
-  a.y = y;
-  a.y_stride = y_stride;
-  a.T = (int)T;
-  a.hop = plan->hop;
-  a.scale = (float)plan->scale;
-  a.eps = 0.f;
-  a.inv_kk = (float)(12.0 / ((double)N * ((double)N * N - 1.0)));
-  a.detrend = plan->detrend;
-  a.flags = 0;
-  a.out = out;
-  a.F_out = N / 2 + 1;
-  a.window = plan->d_window;
-  a.twiddle = plan->d_twiddle;
-  a.dc_alpha = plan->dc_alpha;
-  a.dc_beta = plan->dc_beta;
-  a.dc_coef = plan->d_dc;
-  hipError_t e = hipSuccess;
-  switch (N) {
-    case 64: e = launch_team_mode<64, 3>(a, batch, nullptr, stream, launched); break;
-    case 128: e = launch_team_mode<128, 3>(a, batch, nullptr, stream, launched); break;
-    case 256: e = launch_team_mode<256, 3>(a, batch, nullptr, stream, launched); break;
-    case 512: e = launch_team_mode<512, 3>(a, batch, nullptr, stream, launched); break;
-    case 1024: e = launch_team_mode<1024, 3>(a, batch, nullptr, stream, launched); break;
-    default: break;
-  }
-  if (e != hipSuccess)
-    return set_error(SPECENH_EHIP, std::string("csd team launch: ") + hipGetErrorString(e));
-  return SPECENH_OK;
-}
-
-}  // namespace specenh

@@ -30,6 +30,7 @@
 #include "fft_common.hpp"
 #include "specenh.h"
 #include "runtime.hpp"
+#include "wave.hpp"
 
 namespace specenh {
 
@@ -847,31 +848,12 @@ __device__ __forceinline__ void prod8m(const float* sA, const float* sB, int r, 
   __syncthreads();
 }
 
-// lane `src`'s v (wave-uniform src, a compile-time constant at the call sites)
-__device__ __forceinline__ double readlane_f64(double v, int src) {
-  const long long u = __builtin_bit_cast(long long, v);
-  const int lo = __builtin_amdgcn_readlane((int)u, src);
-  const int hi = __builtin_amdgcn_readlane((int)(u >> 32), src);
-  return __builtin_bit_cast(double, ((long long)hi << 32) | (long long)(unsigned)lo);
-}
-
-// fp64 1/x and 1/sqrt(x) from v_rcp_f64 / v_rsq_f64 and two Newton steps (full fp64
-// precision for finite x != 0 / x > 0): the IEEE division and sqrt sequences sat on the
-// critical path of every Jacobi round (the angle is computed once per pair, then rounded to
-// fp32 for the rotation).
+// fp64 1/x and 1/sqrt(x) through rcp64_2 / rsq64<2> (wave.hpp): the IEEE division and sqrt
+// sequences sat on the critical path of every Jacobi round (the angle is computed once per
+// pair, then rounded to fp32 for the rotation).
 #ifndef SPECENH_SS_EXACT_ANGLE
 #define SPECENH_SS_EXACT_ANGLE 0
 #endif
-__device__ __forceinline__ double rcp64_2(double x) {
-  double r = __builtin_amdgcn_rcp(x);
-  r = fma(r, fma(-x, r, 1.0), r);
-  return fma(r, fma(-x, r, 1.0), r);
-}
-__device__ __forceinline__ double rsq64_2(double x) {
-  double r = __builtin_amdgcn_rsq(x);
-  r = fma(r * fma(-0.5 * x, r * r, 0.5), 1.0, r);      // r (1 + (1 - x r^2) / 2)
-  return fma(r * fma(-0.5 * x, r * r, 0.5), 1.0, r);
-}
 // Orthonormalise the columns of Y (r x P, LDS) into Z with CholeskyQR in fp64:
 // S = Y^T Y, S = R^T R, Z = Y R^-1. fp64 keeps the Gram of Y (condition up to ~1e12
 // here) factorisable; callers run it twice (CholeskyQR2) for fp32-level orthogonality.
@@ -924,17 +906,17 @@ __device__ __forceinline__ void cholqr(const float* sY, float* sZ, int r, double
     for (int i = 0; i < P; ++i) col[i] = (j < P && i <= j) ? sS[i * P + j] : 0.0;
 #pragma unroll
     for (int k = 0; k < P; ++k) {
-      double d = readlane_f64(col[k], k);
+      double d = readlane64(col[k], k);
       if (SPECENH_SS_EXACT_ANGLE) {
         d = d > 0.0 ? sqrt(d) : 1e-300;  // rank-deficient: keep going, column ~ 0
         col[k] = j == k ? d : col[k] / d;  // row k of R (lanes j > k; j < k hold zeros)
       } else {  // the same from one v_rsq_f64 + Newton steps (the pivot's critical path)
-        const double ri = d > 0.0 ? rsq64_2(d) : 1e300;
+        const double ri = d > 0.0 ? rsq64<2>(d) : 1e300;
         col[k] = j == k ? (d > 0.0 ? d * ri : 1e-300) : col[k] * ri;
       }
 #pragma unroll
       for (int i = k + 1; i < P; ++i) {  // trailing S[i][j] -= R[k][i] R[k][j], j >= i
-        const double rki = readlane_f64(col[k], i);
+        const double rki = readlane64(col[k], i);
         if (j >= i) col[i] -= rki * col[k];
       }
     }
@@ -990,8 +972,8 @@ __device__ __forceinline__ void jacobi_angle(double haa, double hbb, double hab,
   }
   const double tau = (hbb - haa) * rcp64_2(2.0 * hab);
   const double u = fma(tau, tau, 1.0);
-  const double tt = copysign(rcp64_2(fabs(tau) + u * rsq64_2(u)), tau >= 0 ? 1.0 : -1.0);
-  c = rsq64_2(fma(tt, tt, 1.0));
+  const double tt = copysign(rcp64_2(fabs(tau) + u * rsq64<2>(u)), tau >= 0 ? 1.0 : -1.0);
+  c = rsq64<2>(fma(tt, tt, 1.0));
   s = tt * c;
 }
 
@@ -1419,15 +1401,6 @@ void subspace_kernel(const float* G, int r, int K,
 #undef CQ_SUB
 }
 
-// Workgroup barrier that orders LDS only: waits for this wave's LDS operations, not for
-// its global loads (__syncthreads' release fence would also drain vmcnt, i.e. wait for the
-// next matrix's prefetch at the first barrier after it is issued).
-__device__ __forceinline__ void lds_sync() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-
 // ---------------------------------------------------------------- 3. reconstruction
 // Workgroup = (matrix, block of RB X-rows). With X_blk (RB x r), V (r x K):
 //   Y = X_blk V_K                       (RB x K)      phase 1
@@ -1773,9 +1746,9 @@ __global__ __launch_bounds__(256, 2) void recon_stream_kernel(
     const int k0 = blk * RB, rows = min(RB, Kr - k0);
     // (LDS-only barriers: __syncthreads' release fence drains vmcnt, i.e. it waited for the
     // prefetched blocks at the first barrier after their loads were issued)
-    lds_sync();  // the previous block's products are done with sX / sY (and sV staged)
+    lds_barrier();  // the previous block's products are done with sX / sY (and sV staged)
     stage(st);
-    lds_sync();
+    lds_barrier();
     // block blk + 2 into the registers just staged: in flight behind two blocks' products
     fetch(st, k0 + 2 * RB, blk + 2 < blk1 ? min(RB, Kr - k0 - 2 * RB) : 0);
     // ---- phase 1: Y = X_blk V
@@ -1812,13 +1785,13 @@ __global__ __launch_bounds__(256, 2) void recon_stream_kernel(
         for (int j = 0; j < 4; ++j) yp[j * PY] = acc[j];
       }
     }
-    lds_sync();
+    lds_barrier();
     if constexpr (KS == 2) {
       for (int e = tid; e < RB * KPP; e += 256) {
         const int row = e / KPP, c = e % KPP;
         sY[row * PY + c] += sY[RB * PY + row * PY + c];
       }
-      lds_sync();
+      lds_barrier();
     }
     // ---- phase 2: out = [X_blk -] Y V^T
     for (int t = wave; t < 2 * nit; t += 4) {
@@ -1893,14 +1866,6 @@ __device__ __forceinline__ int xz_chunk(int g, int j) {
 // X | Zt (4 x ZP, basis transposed) | U (N x 4) | part (4 waves x N x 4) | reduction scratch
 constexpr size_t LDS_BYTES = (size_t)N * LD * 4 + 4 * ZP * 4 + N * 4 * 4 + 4 * N * 4 * 4 + 64 * 8;
 
-
-// 1/sqrt(d) for d > 0: v_rsq_f64 plus one Newton step (the factors below only need to be
-// consistent with each other, not correctly rounded)
-__device__ __forceinline__ double rsq64(double d) {
-  const double r = __builtin_amdgcn_rsq(d);
-  return r * fma(-0.5 * d * r, r, 1.5);
-}
-
 // 4 x 4 Cholesky M = L L^T (lower) in fp64, returned as the strictly lower part of L and
 // rinv = 1 / diag(L). A pivot below 1e-20 of its diagonal entry marks the column dead (its
 // vector lies in the span of the earlier ones, or is zero): rinv = 0, column of L zero.
@@ -1911,7 +1876,7 @@ __device__ __forceinline__ void chol4(const double (&M)[4][4], double (&L)[4][4]
 #pragma unroll
     for (int l = 0; l < j; ++l) d = fma(-L[j][l], L[j][l], d);
     const bool live = d > 1e-20 * M[j][j] && d > 0.0;
-    rinv[j] = live ? rsq64(d) : 0.0;
+    rinv[j] = live ? rsq64<1>(d) : 0.0;
     L[j][j] = 0.0;
 #pragma unroll
     for (int k = j + 1; k < 4; ++k) {
@@ -1981,29 +1946,6 @@ __device__ __forceinline__ void jacobi4(float (&A)[4][4], float (&Q)[4][4]) {
   }
 }
 
-template <int CTRL>
-__device__ __forceinline__ double dpp64(double v) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)b, CTRL, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xF, 0xF, false);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
-__device__ __forceinline__ double readlane64(double v, int l) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_readlane((int)b, l);
-  const int hi = __builtin_amdgcn_readlane((int)(b >> 32), l);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
-// sum over the 64 lanes of a wave (every lane active): DPP inside rows of 16 (quad
-// swaps, half-row and row mirrors), then the four row sums; no LDS traffic
-__device__ __forceinline__ double wave_sum64(double v) {
-  v += dpp64<0xB1>(v);   // quad_perm [1, 0, 3, 2]
-  v += dpp64<0x4E>(v);   // quad_perm [2, 3, 0, 1]
-  v += dpp64<0x141>(v);  // row_half_mirror
-  v += dpp64<0x140>(v);  // row_mirror
-  return (readlane64(v, 0) + readlane64(v, 16)) + (readlane64(v, 32) + readlane64(v, 48));
-}
-
 // Sum NV doubles over the 128 threads of waves 0 and 1 (waves 2, 3 skip the wave sums);
 // every thread returns the totals. One barrier; the caller separates reuse of sR.
 template <int NV>
@@ -2011,12 +1953,12 @@ __device__ __forceinline__ void bsum128(double (&v)[NV], double* sR) {
   const int tid = threadIdx.x, w = tid >> 6;
   if (w < 2) {
 #pragma unroll
-    for (int j = 0; j < NV; ++j) v[j] = wave_sum64(v[j]);
+    for (int j = 0; j < NV; ++j) v[j] = wave_sum_dpp(v[j]);
     if ((tid & 63) == 0)
 #pragma unroll
       for (int j = 0; j < NV; ++j) sR[w * NV + j] = v[j];
   }
-  lds_sync();
+  lds_barrier();
 #pragma unroll
   for (int j = 0; j < NV; ++j) v[j] = sR[j] + sR[NV + j];
 }
@@ -2045,11 +1987,11 @@ __device__ __forceinline__ void gram_sums(const float* sY, const float* sZt, con
       s = fma((double)va, (double)vb, s);
     }
   }
-  s += dpp64<0xB1>(s);   // quad_perm [1, 0, 3, 2]
-  s += dpp64<0x4E>(s);   // quad_perm [2, 3, 0, 1]
-  s += dpp64<0x141>(s);  // row_half_mirror: the two quads of each 8-lane group
+  s += dpp<0xB1, false>(s);   // quad_perm [1, 0, 3, 2]
+  s += dpp<0x4E, false>(s);   // quad_perm [2, 3, 0, 1]
+  s += dpp<0x141, false>(s);  // row_half_mirror: the two quads of each 8-lane group
   if (c == 0 && j < NV) sRed[j] = s;
-  lds_sync();
+  lds_barrier();
 }
 
 // symmetric 4 x 4 from the 10 upper-triangle sums at p (gram_sums order)
@@ -2141,7 +2083,7 @@ __global__ __launch_bounds__(256, 2) void top1_kernel(XView x, int Kr, int r, fl
     for (int p = 0; p < 4; ++p)  // column 0 all ones (close to v1 for the non-negative
                                    // log spectrograms), the others pseudo-random
       sZt[zt(p, tid)] = tid < r ? (p == 0 ? 1.f : hash_unit(tid, p)) : 0.f;
-  lds_sync();
+  lds_barrier();
   const double tr = (sR[32] + sR[33]) + (sR[34] + sR[35]);
   T1_MARK(0);
 
@@ -2198,7 +2140,7 @@ __global__ __launch_bounds__(256, 2) void top1_kernel(XView x, int Kr, int r, fl
       }
       *reinterpret_cast<float2*>(sU + 4 * (kb + 32 * (g >> 1)) + 2 * b3) = make_float2(a2[0], a2[1]);
     }
-    lds_sync();
+    lds_barrier();
     T1_MARK(1);
     {  // Y = X^T U: wave w sums its 32 rows, lane halves 16 each
       float a[16];  // [column q][p]
@@ -2228,7 +2170,7 @@ __global__ __launch_bounds__(256, 2) void top1_kernel(XView x, int Kr, int r, fl
       *reinterpret_cast<float4*>(dst + 4 * ppos(4 * cc + 2 * h)) = make_float4(a8[0], a8[1], a8[2], a8[3]);
       *reinterpret_cast<float4*>(dst + 4 * ppos(4 * cc + 2 * h + 1)) = make_float4(a8[4], a8[5], a8[6], a8[7]);
     }
-    lds_sync();
+    lds_barrier();
     if (tid < N) {
       const int pt = ppos(tid);
       float4 s = *reinterpret_cast<const float4*>(sP + 4 * pt);
@@ -2247,7 +2189,7 @@ __global__ __launch_bounds__(256, 2) void top1_kernel(XView x, int Kr, int r, fl
 #pragma unroll
       for (int p = 0; p < 4; ++p) y[p] = z[p] = uk[p] = 0.f;
     }
-    lds_sync();
+    lds_barrier();
     // Rayleigh-Ritz + residual test at rounds 2, 3, 4, then every second round
     T1_MARK(2);
     const bool check = t >= 2 && (t <= 4 || t % 2 == 0 || t == MAX_ROUNDS);  // uniform
@@ -2315,7 +2257,7 @@ __global__ __launch_bounds__(256, 2) void top1_kernel(XView x, int Kr, int r, fl
         gv = fma((double)y[p], q1[p], gv);  // (G v)_i
       }
       double rs[3] = {gv * vi, vi * vi, gv * gv};
-      lds_sync();  // sR reuse
+      lds_barrier();  // sR reuse
       bsum128<3>(rs, sR + 40);
       // fp64 Rayleigh quotient theta = v^T G v / v^T v and the residual of the normalised
       // v: ||G v - theta v||^2 / ||v||^2 = (g.g - theta g.v) / v.v
@@ -2333,7 +2275,7 @@ __global__ __launch_bounds__(256, 2) void top1_kernel(XView x, int Kr, int r, fl
       if (conv || t >= MAX_ROUNDS) {  // uniform
         bad = conv ? 0 : 1;
         t_used = t;
-        if (tid < N) vd[tid] = vi * rsq64(vv);  // v / ||v|| (partials were read above)
+        if (tid < N) vd[tid] = vi * rsq64<1>(vv);  // v / ||v|| (partials were read above)
         T1_MARK(4);
         break;
       }
@@ -2355,7 +2297,7 @@ __global__ __launch_bounds__(256, 2) void top1_kernel(XView x, int Kr, int r, fl
 #pragma unroll
       for (int p = 0; p < 4; ++p) sZt[zt(p, tid)] = (float)zd[p];
     }
-    lds_sync();
+    lds_barrier();
     T1_MARK(3);
   }
   // ---- one power step in fp64 from the converged v: v <- X^T X v / ||X^T X v||, then
@@ -2377,11 +2319,11 @@ __global__ __launch_bounds__(256, 2) void top1_kernel(XView x, int Kr, int r, fl
       s1 = fma((double)x4.w, v23.y, s1);
     }
     if (h) hd[k] = s0 + s1;
-    lds_sync();
+    lds_barrier();
     if (!h) ud[k] = (s0 + s1) + hd[k];
-    lds_sync();
+    lds_barrier();
   };
-  lds_sync();
+  lds_barrier();
   Xv();
   {  // w = X^T u: thread (column i, row half h); v = w / ||w||
     const int i = tid & (N - 1), h = tid >> 7;
@@ -2393,12 +2335,12 @@ __global__ __launch_bounds__(256, 2) void top1_kernel(XView x, int Kr, int r, fl
       s1 = fma((double)sX[(k + 1) * LD + i], ud[k + 1], s1);
     }
     if (h) hd[i] = s0 + s1;
-    lds_sync();
+    lds_barrier();
     const double w = h ? 0.0 : (s0 + s1) + hd[i];
     double nn[1] = {w * w};
     bsum128<1>(nn, sR + 40);
-    if (!h) vd[i] = nn[0] > 0.0 ? w * rsq64(nn[0]) : 0.0;
-    lds_sync();
+    if (!h) vd[i] = nn[0] > 0.0 ? w * rsq64<1>(nn[0]) : 0.0;
+    lds_barrier();
   }
   Xv();
   T1_MARK(5);
@@ -2521,16 +2463,6 @@ __global__ __launch_bounds__(256) void gram64_kernel(XView x, int K, int r, doub
     gram64_one(x, K, r, G, nts, b, blockIdx.x);
     __syncthreads();  // (LDS reused by the next matrix)
   }
-}
-
-
-__device__ __forceinline__ double block_sum256(double v, double* red) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  __syncthreads();  // red is reused call after call
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
 // Householder tridiagonalisation of the symmetric n x n fp64 matrix A (in place, global,
@@ -3043,6 +2975,18 @@ using namespace specenh;
 
 namespace {
 
+// A CU's LDS: what the kernels whose dynamic LDS follows the shape are opted in to, once per
+// device (allow_lds); each launcher still checks the size it actually asks for.
+constexpr int kMaxLds = 160 * 1024;
+
+// f(TO{}) with TO the output element type of `odt`
+template <class F>
+auto with_out_type(int odt, F&& f) {
+  if (odt == SPECENH_DTYPE_F16) return f(_Float16{});
+  if (odt == SPECENH_DTYPE_BF16) return f(__bf16{});
+  return f(float{});
+}
+
 // G = X^T X for every matrix: the LDS-chunked kernel for r <= 128 (r % 4 == 0), else
 // one wave per 32x32 tile.
 void launch_gram(const XView& xv, int Kr, int r, float* G, long long batch, hipStream_t st) {
@@ -3080,9 +3024,9 @@ hipError_t launch_subspace_t(const float* G, int r, int K, float* V, float* thet
                              long long batch, hipStream_t st, int cut2, int* flags, int seed,
                              const int* only) {
   const size_t lds = SsLayout<P>::bytes(r);
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
-  hipError_t e = hipFuncSetAttribute((const void*)subspace_kernel<P>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (lds > kMaxLds) return hipErrorInvalidValue;
+  static LdsOptIn lds_site;
+  hipError_t e = allow_lds(lds_site, {(const void*)subspace_kernel<P>}, kMaxLds);
   if (e != hipSuccess) return e;
   // 3 rounds when the subspace oversamples the wanted K by >= 8 columns, else 5
   // (a second pass over flagged matrices starts elsewhere and iterates 4x longer)
@@ -3110,6 +3054,13 @@ template <int KP, typename TO>
 hipError_t launch_recon_t(XView xb, int Kr, int r, const float* V, int K, int lo, int hi,
                           int comp, const int* only, void* out, long long ob, long long osk,
                           long long osi, long long nb, hipStream_t st) {
+  static LdsOptIn lds_site;
+  const hipError_t e = allow_lds(
+      lds_site,
+      {(const void*)recon_stream_kernel<KP, TO, true>, (const void*)recon_stream_kernel<KP, TO, false>,
+       (const void*)recon_mfma_kernel<KP, TO>, (const void*)recon_kernel<KP, TO>},
+      kMaxLds);
+  if (e != hipSuccess) return e;
   if (variant(V_SVD_RECON_VALU) == 0) {  // the matrix-core reconstruction
     constexpr int NT = (KP + 15) / 16, KPP = 16 * NT, KS = 2 * NT < 4 ? 2 : 1;
     const int RP = (r + 15) & ~15;
@@ -3119,7 +3070,7 @@ hipError_t launch_recon_t(XView xb, int Kr, int r, const float* V, int K, int lo
     const bool rowmaj16 = xb.si == 1 && r % 4 == 0 && xb.sk % 4 == 0 &&
                           xb.batch_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(xb.base) & 15) == 0;
     const bool trans = xb.sk == 1 && xb.si != 1;
-    if (lm <= 160 * 1024 && r <= 256 && (rowmaj16 || trans) &&
+    if (lm <= kMaxLds && r <= 256 && (rowmaj16 || trans) &&
         variant(V_SVD_RECON_BLOCKS) == 0) {
       const int nblk = (Kr + RB - 1) / RB;
       // enough workgroups for ~4 per CU, each a run of consecutive blocks of one matrix
@@ -3127,10 +3078,6 @@ hipError_t launch_recon_t(XView xb, int Kr, int r, const float* V, int K, int lo
       const int segs = (int)std::max(1LL, std::min<long long>(nblk, (want + nb - 1) / nb));
       const int bps = (nblk + segs - 1) / segs;
       const int grid_x = (nblk + bps - 1) / bps;
-      const void* kfn = trans ? (const void*)recon_stream_kernel<KP, TO, true>
-                              : (const void*)recon_stream_kernel<KP, TO, false>;
-      hipError_t e = hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lm);
-      if (e != hipSuccess) return e;
       if (trans)
         SPECENH_LAUNCH((recon_stream_kernel<KP, TO, true>), dim3(grid_x, (unsigned)nb), dim3(256),
                        lm, st, xb, Kr, r, V, K, lo, hi, comp, only, reinterpret_cast<TO*>(out),
@@ -3141,10 +3088,7 @@ hipError_t launch_recon_t(XView xb, int Kr, int r, const float* V, int K, int lo
                        ob, osk, osi, bps);
       return hipGetLastError();
     }
-    if (lm <= 160 * 1024) {
-      hipError_t e = hipFuncSetAttribute((const void*)recon_mfma_kernel<KP, TO>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lm);
-      if (e != hipSuccess) return e;
+    if (lm <= kMaxLds) {
       SPECENH_LAUNCH((recon_mfma_kernel<KP, TO>), dim3((Kr + RB - 1) / RB, (unsigned)nb),
                      dim3(256), lm, st, xb, Kr, r, V, K, lo, hi, comp, only,
                      reinterpret_cast<TO*>(out), ob, osk, osi);
@@ -3152,10 +3096,7 @@ hipError_t launch_recon_t(XView xb, int Kr, int r, const float* V, int K, int lo
     }
   }
   const size_t lds = (size_t)r * KP * 4 + (size_t)RB * (r + 1) * 4 + (size_t)RB * KP * 4;
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
-  hipError_t e = hipFuncSetAttribute((const void*)recon_kernel<KP, TO>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
+  if (lds > kMaxLds) return hipErrorInvalidValue;
   SPECENH_LAUNCH((recon_kernel<KP, TO>), dim3((Kr + RB - 1) / RB, (unsigned)nb), dim3(256),
                      lds, st, xb, Kr, r, V, K, lo, hi, comp, only, reinterpret_cast<TO*>(out),
                      ob, osk, osi);
@@ -3175,16 +3116,6 @@ hipError_t launch_recon_k(int KP, XView xb, int Kr, int r, const float* V, int K
 #undef SPECENH_RC
     default: return hipErrorInvalidValue;
   }
-}
-
-hipError_t launch_recon(int KP, XView xb, int Kr, int r, const float* V, int K, int lo, int hi,
-                        int comp, const int* only, void* out, long long ob, long long osk,
-                        long long osi, long long nb, hipStream_t st, int odt = SPECENH_DTYPE_F32) {
-  if (odt == SPECENH_DTYPE_F16)
-    return launch_recon_k<_Float16>(KP, xb, Kr, r, V, K, lo, hi, comp, only, out, ob, osk, osi, nb, st);
-  if (odt == SPECENH_DTYPE_BF16)
-    return launch_recon_k<__bf16>(KP, xb, Kr, r, V, K, lo, hi, comp, only, out, ob, osk, osi, nb, st);
-  return launch_recon_k<float>(KP, xb, Kr, r, V, K, lo, hi, comp, only, out, ob, osk, osi, nb, st);
 }
 
 size_t dtype_size(int dt) { return dt == SPECENH_DTYPE_F32 ? 4 : 2; }
@@ -3247,28 +3178,24 @@ __global__ __launch_bounds__(256) void eig_fallback_kernel(
   }
 }
 
+// dynamic LDS of recon_eig_one (r <= EIG_MAXN: the eigen path's limit)
+constexpr size_t recon_eig_lds(int r) {
+  return (size_t)RB * (r + 1) * 4 + (size_t)r * 33 * 4 + (size_t)RB * 33 * 4;
+}
+
 template <typename TO>
 hipError_t launch_recon_eig_t(XView xb, int Kr, int r, const double* Z, long long ld,
                               const int* kinfo, void* out, long long ob, long long osk,
                               long long osi, long long nb, hipStream_t st, const int* only) {
-  const size_t lds = (size_t)RB * (r + 1) * 4 + (size_t)r * 33 * 4 + (size_t)RB * 33 * 4;
-  hipError_t e = hipFuncSetAttribute((const void*)recon_eig_kernel<TO>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  const size_t lds = recon_eig_lds(r);
+  static LdsOptIn lds_site;
+  hipError_t e =
+      allow_lds(lds_site, {(const void*)recon_eig_kernel<TO>}, (int)recon_eig_lds(EIG_MAXN));
   if (e != hipSuccess) return e;
   const unsigned gm = only ? (unsigned)std::min<long long>(nb, 2LL * device_cus()) : (unsigned)nb;
   SPECENH_LAUNCH(recon_eig_kernel<TO>, dim3((Kr + RB - 1) / RB, gm), dim3(256), lds, st, xb, Kr,
                  r, Z, ld, kinfo, reinterpret_cast<TO*>(out), ob, osk, osi, only, nb);
   return hipGetLastError();
-}
-
-hipError_t launch_recon_eig(int odt, XView xb, int Kr, int r, const double* Z, long long ld,
-                            const int* kinfo, void* out, long long ob, long long osk,
-                            long long osi, long long nb, hipStream_t st, const int* only) {
-  if (odt == SPECENH_DTYPE_F16)
-    return launch_recon_eig_t<_Float16>(xb, Kr, r, Z, ld, kinfo, out, ob, osk, osi, nb, st, only);
-  if (odt == SPECENH_DTYPE_BF16)
-    return launch_recon_eig_t<__bf16>(xb, Kr, r, Z, ld, kinfo, out, ob, osk, osi, nb, st, only);
-  return launch_recon_eig_t<float>(xb, Kr, r, Z, ld, kinfo, out, ob, osk, osi, nb, st, only);
 }
 
 template <typename TO>
@@ -3277,9 +3204,10 @@ hipError_t launch_eig_fallback_t(XView xb, int Kr, int r, double* G, int nts, do
                                  double* fac, long long ld, int* kinfo, void* out, long long ob,
                                  long long osk, long long osi, const int* only, long long nb,
                                  unsigned gm, hipStream_t st) {
-  const size_t lds = (size_t)RB * (r + 1) * 4 + (size_t)r * 33 * 4 + (size_t)RB * 33 * 4;
-  hipError_t e = hipFuncSetAttribute((const void*)eig_fallback_kernel<TO>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  const size_t lds = recon_eig_lds(r);
+  static LdsOptIn lds_site;
+  hipError_t e =
+      allow_lds(lds_site, {(const void*)eig_fallback_kernel<TO>}, (int)recon_eig_lds(EIG_MAXN));
   if (e != hipSuccess) return e;
   SPECENH_LAUNCH(eig_fallback_kernel<TO>, dim3(gm), dim3(256), lds, st, xb, Kr, r, G, nts, dg,
                  eg, taug, lo, hi, Z, fac, ld, kinfo, reinterpret_cast<TO*>(out), ob, osk, osi,
@@ -3287,19 +3215,16 @@ hipError_t launch_eig_fallback_t(XView xb, int Kr, int r, double* G, int nts, do
   return hipGetLastError();
 }
 
-hipError_t launch_eig_fallback(int odt, XView xb, int Kr, int r, double* G, int nts, double* dg,
-                               double* eg, double* taug, int lo, int hi, double* Z, double* fac,
-                               long long ld, int* kinfo, void* out, long long ob, long long osk,
-                               long long osi, const int* only, long long nb, unsigned gm,
-                               hipStream_t st) {
-  if (odt == SPECENH_DTYPE_F16)
-    return launch_eig_fallback_t<_Float16>(xb, Kr, r, G, nts, dg, eg, taug, lo, hi, Z, fac, ld,
-                                           kinfo, out, ob, osk, osi, only, nb, gm, st);
-  if (odt == SPECENH_DTYPE_BF16)
-    return launch_eig_fallback_t<__bf16>(xb, Kr, r, G, nts, dg, eg, taug, lo, hi, Z, fac, ld,
-                                         kinfo, out, ob, osk, osi, only, nb, gm, st);
-  return launch_eig_fallback_t<float>(xb, Kr, r, G, nts, dg, eg, taug, lo, hi, Z, fac, ld, kinfo,
-                                      out, ob, osk, osi, only, nb, gm, st);
+// X orientation: the Gram matrix is taken over the smaller dimension, so X = A (m >= n) or
+// X = A^T; Kr rows of X, and (osk, osi) the output strides of X's row and column index
+struct Oriented {
+  XView xv;
+  int Kr;
+  long long osk, osi;
+};
+Oriented orient(const float* A, int m, int n, long long a_stride) {
+  if (m >= n) return {{A, a_stride, n, 1}, m, n, 1};
+  return {{A, a_stride, 1, n}, n, 1, n};
 }
 
 // The eigen path over the whole batch, chunk by chunk (stream-ordered, no host sync).
@@ -3325,15 +3250,10 @@ int eig_denoise(const float* A, long long batch, int m, int n, long long a_strid
   int* ranges = kinfo + 2 * ch;
   int* num = ranges + 2 * ch;
   double* med = (double*)(((uintptr_t)(num + ch) + 7) & ~(uintptr_t)7);
-  XView xv;
-  xv.batch_stride = a_stride;
-  int Kr;
-  long long osk, osi;
-  if (m >= n) {
-    xv.sk = n; xv.si = 1; Kr = m; osk = n; osi = 1;
-  } else {
-    xv.sk = 1; xv.si = n; Kr = n; osk = 1; osi = n;
-  }
+  const Oriented o = orient(A, m, n, a_stride);
+  XView xv = o.xv;  // (base moves with the chunk)
+  const int Kr = o.Kr;
+  const long long osk = o.osk, osi = o.osi;
   const long long ob = (long long)m * n;
   const size_t osz = dtype_size(odt);
   const int nts64 = (r + 63) / 64, ntri64 = nts64 * (nts64 + 1) / 2;
@@ -3345,6 +3265,7 @@ int eig_denoise(const float* A, long long batch, int m, int n, long long a_strid
     const long long nb = std::min(ch, batch - b0);
     xv.base = A + b0 * a_stride;
     const int* on = only ? only + b0 : nullptr;
+    void* ob0 = static_cast<char*>(out) + (size_t)(b0 * ob) * osz;  // this chunk's outputs
     // fallback (on: the flagged few): a grid of at most two workgroups per CU looping over
     // the matrices instead of one per matrix (gram64_kernel's comment). The merged launch
     // takes 32 workgroups (SPECENH_EIG_GRID): in the two-stream C5 step its 58 KB-LDS
@@ -3359,10 +3280,11 @@ int eig_denoise(const float* A, long long batch, int m, int n, long long a_strid
     // tile-parallel grids once many matrices are flagged. Merged only while r * Kr is small.
     const bool merged_fits = (long long)r * Kr <= 128LL * 128;
     if (on && opt_mode < 0 && merged_fits && SPECENH_EIG_MERGED && variant(V_EIG_SPLIT) == 0) {
-      const hipError_t e = launch_eig_fallback(odt, xv, Kr, r, G64, nts64, dd, ee, tau, lo, hi,
-                                               Z, fac, L.ld, kinfo,
-                                               static_cast<char*>(out) + (size_t)(b0 * ob) * osz,
-                                               ob, osk, osi, on, nb, gm, st);
+      const hipError_t e = with_out_type(odt, [&](auto t) {
+        return launch_eig_fallback_t<decltype(t)>(xv, Kr, r, G64, nts64, dd, ee, tau, lo, hi, Z,
+                                                  fac, L.ld, kinfo, ob0, ob, osk, osi, on, nb, gm,
+                                                  st);
+      });
       if (e != hipSuccess) return set_error(SPECENH_EHIP, std::string("eigen fallback: ") + hipGetErrorString(e));
       continue;
     }
@@ -3386,9 +3308,10 @@ int eig_denoise(const float* A, long long batch, int m, int n, long long a_strid
     SPECENH_LAUNCH(eigvec_kernel, dim3(gm), dim3(256), 0, st, G64, dd, ee, tau, r, lo, hi, rg,
                    Z, fac, L.ld, kinfo, on, nb);
     if (hipGetLastError() != hipSuccess) return set_error(SPECENH_EHIP, "eigen path launch");
-    const hipError_t e = launch_recon_eig(odt, xv, Kr, r, Z, L.ld, kinfo,
-                                          static_cast<char*>(out) + (size_t)(b0 * ob) * osz, ob,
-                                          osk, osi, nb, st, on);
+    const hipError_t e = with_out_type(odt, [&](auto t) {
+      return launch_recon_eig_t<decltype(t)>(xv, Kr, r, Z, L.ld, kinfo, ob0, ob, osk, osi, nb, st,
+                                             on);
+    });
     if (e != hipSuccess) return set_error(SPECENH_EHIP, std::string("recon: ") + hipGetErrorString(e));
   }
   return SPECENH_OK;
@@ -3404,20 +3327,12 @@ bool top1_fits(const float* A, int m, int n, long long a_stride) {
 template <typename TO>
 hipError_t launch_top1_t(const float* A, long long batch, int m, int n, long long a_stride,
                          int* flags, void* out, hipStream_t st, long long* phase_clk) {
-  const hipError_t attr = hipFuncSetAttribute(
-      (const void*)top1_kernel<TO>, hipFuncAttributeMaxDynamicSharedMemorySize,
-      (int)top1::LDS_BYTES);
+  static LdsOptIn lds_site;
+  const hipError_t attr =
+      allow_lds(lds_site, {(const void*)top1_kernel<TO>}, (int)top1::LDS_BYTES);
   if (attr != hipSuccess) return attr;
-  XView xv;
-  xv.base = A;
-  xv.batch_stride = a_stride;
-  int Kr, r = std::min(m, n);
-  long long osk, osi;
-  if (m >= n) {
-    xv.sk = n; xv.si = 1; Kr = m; osk = n; osi = 1;
-  } else {
-    xv.sk = 1; xv.si = n; Kr = n; osk = 1; osi = n;
-  }
+  const auto [xv, Kr, osk, osi] = orient(A, m, n, a_stride);
+  const int r = std::min(m, n);
   for (long long b0 = 0; b0 < batch; b0 += 1LL << 30) {  // one workgroup per matrix
     const long long nb = std::min<long long>(1LL << 30, batch - b0);
     XView xb = xv;
@@ -3427,15 +3342,6 @@ hipError_t launch_top1_t(const float* A, long long batch, int m, int n, long lon
                    (long long)m * n, osk, osi, nb, phase_clk ? phase_clk + 8 * b0 : nullptr);
   }
   return hipGetLastError();
-}
-
-hipError_t launch_top1(const float* A, long long batch, int m, int n, long long a_stride,
-                       int* flags, void* out, int odt, hipStream_t st, long long* phase_clk) {
-  if (odt == SPECENH_DTYPE_F16)
-    return launch_top1_t<_Float16>(A, batch, m, n, a_stride, flags, out, st, phase_clk);
-  if (odt == SPECENH_DTYPE_BF16)
-    return launch_top1_t<__bf16>(A, batch, m, n, a_stride, flags, out, st, phase_clk);
-  return launch_top1_t<float>(A, batch, m, n, a_stride, flags, out, st, phase_clk);
 }
 
 // denoising_by_svd.ipynb:224-228: clamp start < 0 and stop > r, then Python slicing
@@ -3459,6 +3365,36 @@ int range_path(int r, int lo, int hi, int& K) {
              ? 1
              : 2;
 }
+
+// Workspace of the subspace path, as byte offsets: G (r x r), V (r x K) and theta (K) per
+// matrix in fp32; for r <= EIG_MAXN also the per-matrix convergence flags of the two subspace
+// passes and the eigen-path region that redoes what stays flagged, each 256-byte aligned
+// (flags == 0 otherwise: no fallback). The size query and both users take the layout from here.
+struct SubspaceWs {
+  size_t G, V, theta, flags, flags2, eig, total;
+};
+SubspaceWs subspace_ws(long long batch, long long r, int K) {
+  SubspaceWs w{};
+  w.V = (size_t)(batch * r * r) * sizeof(float);
+  w.theta = (size_t)(batch * r * r + batch * r * K) * sizeof(float);
+  w.total = (size_t)(batch * r * r + batch * r * K + batch * K) * sizeof(float);
+  if (r > EIG_MAXN) return w;
+  w.flags = (w.total + 255) / 256 * 256;
+  w.flags2 = w.flags + (size_t)batch * 4;
+  w.eig = (w.flags + 2 * (size_t)batch * 4 + 255) / 256 * 256;
+  w.total = w.eig + eig_layout((int)r).bytes(batch);
+  return w;
+}
+// top1_kernel's workspace (default range [1, r)): its flags and the eigen-path region that
+// redoes the flagged matrices sit where the subspace layout has them, or for r too small
+// for a subspace (path 2) the eigen-path region comes first and the flags follow it.
+SubspaceWs top1_ws(long long batch, int r, int path, int K) {
+  if (path == 1) return subspace_ws(batch, r, K);
+  SubspaceWs w{};
+  w.flags = eig_layout(r).bytes(batch);
+  w.total = w.flags + batch * 4 + 256;
+  return w;
+}
 }  // namespace
 
 extern "C" {
@@ -3467,13 +3403,7 @@ size_t specenh_svd_workspace_bytes(long long batch, int m, int n, int kmax) {
   const long long r = std::min(m, n);
   if (batch <= 0 || r <= 0) return 16;
   if (kmax > PMAX - 8 && r <= EIG_MAXN) return eig_layout((int)r).bytes(batch);
-  // subspace path: G, V, theta; for r <= 256 also the per-matrix convergence flags of the
-  // two subspace passes and the eigen-path workspace that redoes what stays flagged
-  size_t off = (size_t)(batch * r * r + batch * r * kmax + batch * kmax) * sizeof(float);
-  if (r > EIG_MAXN) return off;
-  off = (off + 255) / 256 * 256 + 2 * (size_t)batch * 4;
-  off = (off + 255) / 256 * 256;
-  return off + eig_layout((int)r).bytes(batch);
+  return subspace_ws(batch, r, kmax).total;
 }
 
 size_t specenh_svd_denoise_workspace_bytes(long long batch, int m, int n, int start, int stop) {
@@ -3484,8 +3414,8 @@ size_t specenh_svd_denoise_workspace_bytes(long long batch, int m, int n, int st
   switch (range_path(r, lo, hi, K)) {
     case 1: return specenh_svd_workspace_bytes(batch, m, n, K);
     case 2:  // (+ top1_kernel's flags for the default range)
-      return r <= EIG_MAXN ? eig_layout(r).bytes(batch) + (lo == 1 && hi == r ? batch * 4 + 256 : 0)
-                           : 16;
+      if (r > EIG_MAXN) return 16;
+      return lo == 1 && hi == r ? top1_ws(batch, r, 2, K).total : eig_layout(r).bytes(batch);
     default: return 16;
   }
 }
@@ -3537,27 +3467,20 @@ int specenh_svd_denoise_ex(const float* A, long long batch, int m, int n, long l
   if (lo == 1 && hi == r && top1_fits(A, m, n, a_stride) && variant(V_SVD_NO_TOP1) == 0) {
     // one pass: top1_kernel writes every output and flags the matrices without a converged
     // gap at the cut; the fp64 eigen path redoes those (its kernels return at once for the
-    // others). Workspace: the flags and eigen-path regions of the subspace layout, or for
-    // r too small for a subspace the eigen-path layout followed by the flags.
-    size_t off, eoff;
-    if (path == 1) {
-      off = (size_t)(batch * r * r + batch * (long long)r * K + batch * K) * sizeof(float);
-      off = (off + 255) / 256 * 256;
-      eoff = (off + 2 * (size_t)batch * 4 + 255) / 256 * 256;
-    } else {
-      eoff = 0;
-      off = eig_layout(r).bytes(batch);
-    }
-    int* flags = (int*)((char*)workspace + off);
+    // others).
+    const SubspaceWs ws = top1_ws(batch, r, path, K);
+    int* flags = (int*)((char*)workspace + ws.flags);
 #ifdef SPECENH_TOP1_STATS  // development build: phase clocks into the (unused) Gram region
     long long* phase_clk = path == 1 ? (long long*)workspace : nullptr;
 #else
     long long* phase_clk = nullptr;
 #endif
-    const hipError_t e = launch_top1(A, batch, m, n, a_stride, flags, out, out_dtype, st, phase_clk);
+    const hipError_t e = with_out_type(out_dtype, [&](auto t) {
+      return launch_top1_t<decltype(t)>(A, batch, m, n, a_stride, flags, out, st, phase_clk);
+    });
     if (e != hipSuccess) return set_error(SPECENH_EHIP, std::string("top1: ") + hipGetErrorString(e));
     return eig_denoise(A, batch, m, n, a_stride, 1, r, -1, out, out_dtype, nullptr, nullptr,
-                       nullptr, (char*)workspace + eoff, st, flags);
+                       nullptr, (char*)workspace + ws.eig, st, flags);
   }
   if (path == 2)  // wide or bottom-of-spectrum range: fp64 eigenvectors (r <= 256)
     return eig_denoise(A, batch, m, n, a_stride, lo, hi, -1, out, out_dtype, nullptr, nullptr,
@@ -3568,50 +3491,45 @@ int specenh_svd_denoise_ex(const float* A, long long batch, int m, int n, long l
   const bool complement = (hi == r);
   int p = std::max(8, ((K + 7 + 7) / 8) * 8);
   if (p > r) p = (r / 8) * 8;
-  // X orientation: Gram over the smaller dimension
-  XView xv;
-  xv.base = A;
-  xv.batch_stride = a_stride;
-  int Kr;  // rows of X
-  long long osk, osi;
-  if (m >= n) {
-    xv.sk = n; xv.si = 1; Kr = m; osk = n; osi = 1;
-  } else {
-    xv.sk = 1; xv.si = n; Kr = n; osk = 1; osi = n;
-  }
+  const Oriented o = orient(A, m, n, a_stride);
+  const XView& xv = o.xv;
+  const int Kr = o.Kr;
   if (complement) {  // columns [0, lo) of the top-lo subspace, subtracted from X
     hi = lo;
     lo = 0;
   }
-  float* G = (float*)workspace;
-  float* V = G + batch * (long long)r * r;
-  float* theta = V + batch * (long long)r * K;
-  int* flags = nullptr;   // first subspace pass: cut without a converged gap
-  int* flags2 = nullptr;  // still so after the second pass
-  void* eig_ws = nullptr;
-  if (r <= EIG_MAXN) {
-    size_t off = (size_t)(batch * r * r + batch * (long long)r * K + batch * K) * sizeof(float);
-    off = (off + 255) / 256 * 256;
-    flags = (int*)((char*)workspace + off);
-    flags2 = flags + batch;
-    off = (off + 2 * (size_t)batch * 4 + 255) / 256 * 256;
-    eig_ws = (char*)workspace + off;
-  }
+  const SubspaceWs ws = subspace_ws(batch, r, K);
+  char* const w = (char*)workspace;
+  float* G = (float*)(w + ws.G);
+  float* V = (float*)(w + ws.V);
+  float* theta = (float*)(w + ws.theta);
+  int* flags = ws.flags ? (int*)(w + ws.flags) : nullptr;    // first subspace pass: cut without
+                                                             // a converged gap
+  int* flags2 = ws.flags ? (int*)(w + ws.flags2) : nullptr;  // still so after the second pass
   launch_gram(xv, Kr, r, G, batch, st);
   if (hipGetLastError() != hipSuccess) return set_error(SPECENH_EHIP, "gram launch");
   const int KP = (K + 7) / 8 * 8;
   hipError_t e = launch_subspace(p, G, r, K, V, theta, batch, st,
                                  (!complement && lo > 0) ? lo - 1 : -1, flags);
   if (e != hipSuccess) return set_error(SPECENH_EHIP, std::string("subspace: ") + hipGetErrorString(e));
-  for (long long b0 = 0; b0 < batch; b0 += 65535) {
-    const long long nb = std::min<long long>(65535, batch - b0);
-    XView xb = xv;
-    xb.base = A + b0 * a_stride;
-    e = launch_recon(KP, xb, Kr, r, V + b0 * (long long)r * K, K, lo, hi, complement ? 1 : 0,
-                     nullptr, static_cast<char*>(out) + (size_t)(b0 * ob) * osz, ob, osk, osi, nb,
-                     st, out_dtype);
-    if (e != hipSuccess) return set_error(SPECENH_EHIP, std::string("recon: ") + hipGetErrorString(e));
-  }
+  // the reconstruction of every matrix, or of those `only` marks, 65535 per launch
+  auto recon = [&](const int* only) {
+    for (long long b0 = 0; b0 < batch; b0 += 65535) {
+      const long long nb = std::min<long long>(65535, batch - b0);
+      XView xb = xv;
+      xb.base = A + b0 * a_stride;
+      const hipError_t re = with_out_type(out_dtype, [&](auto t) {
+        return launch_recon_k<decltype(t)>(
+            KP, xb, Kr, r, V + b0 * (long long)r * K, K, lo, hi, complement ? 1 : 0,
+            only ? only + b0 : nullptr, static_cast<char*>(out) + (size_t)(b0 * ob) * osz, ob,
+            o.osk, o.osi, nb, st);
+      });
+      if (re != hipSuccess) return re;
+    }
+    return hipSuccess;
+  };
+  e = recon(nullptr);
+  if (e != hipSuccess) return set_error(SPECENH_EHIP, std::string("recon: ") + hipGetErrorString(e));
   if (hipGetLastError() != hipSuccess) return set_error(SPECENH_EHIP, "recon launch");
   if (!flags) return SPECENH_OK;
   // Flagged matrices: a second subspace pass (other start vectors, 4x the rounds) catches
@@ -3622,21 +3540,14 @@ int specenh_svd_denoise_ex(const float* A, long long batch, int m, int n, long l
   e = launch_subspace(p, G, r, K, V, theta, batch, st, (!complement && lo > 0) ? lo - 1 : -1,
                       flags2, 1, flags);
   if (e != hipSuccess) return set_error(SPECENH_EHIP, std::string("subspace: ") + hipGetErrorString(e));
-  for (long long b0 = 0; b0 < batch; b0 += 65535) {
-    const long long nb = std::min<long long>(65535, batch - b0);
-    XView xb = xv;
-    xb.base = A + b0 * a_stride;
-    e = launch_recon(KP, xb, Kr, r, V + b0 * (long long)r * K, K, lo, hi, complement ? 1 : 0,
-                     flags + b0, static_cast<char*>(out) + (size_t)(b0 * ob) * osz, ob, osk, osi,
-                     nb, st, out_dtype);
-    if (e != hipSuccess) return set_error(SPECENH_EHIP, std::string("recon: ") + hipGetErrorString(e));
-  }
+  e = recon(flags);
+  if (e != hipSuccess) return set_error(SPECENH_EHIP, std::string("recon: ") + hipGetErrorString(e));
   if (complement) {  // back to the kept range [start, r)
     lo = hi;
     hi = r;
   }
   return eig_denoise(A, batch, m, n, a_stride, lo, hi, -1, out, out_dtype, nullptr, nullptr,
-                     nullptr, eig_ws, st, flags2);
+                     nullptr, w + ws.eig, st, flags2);
 }
 
 size_t specenh_svd_optimal_workspace_bytes(long long batch, int m, int n) {

@@ -31,12 +31,12 @@
 
 #include <algorithm>
 #include <cstdint>
-#include <mutex>
 #include <string>
 
 #include "lds_dma.hpp"
 #include "specenh.h"
 #include "runtime.hpp"
+#include "wave.hpp"
 
 #ifndef SPECENH_TAILG_PYSPLIT
 #define SPECENH_TAILG_PYSPLIT 0
@@ -82,13 +82,6 @@ __device__ __forceinline__ uint2 relu_pack(const f32x4& v) {
     return uint2{pack2<T>(fmaxf(v[0], 0.f), fmaxf(v[1], 0.f)),
                  pack2<T>(fmaxf(v[2], 0.f), fmaxf(v[3], 0.f))};
   }
-}
-
-// workgroup barrier ordering LDS only (the register prefetch loads stay in flight)
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
 }
 
 constexpr int gcd_c(int a, int b) { return b ? gcd_c(b, a % b) : a; }
@@ -482,12 +475,9 @@ __global__ __launch_bounds__((TG<CO, KT, KO>::THREADS)) void tailg_kernel(TGArgs
 template <typename T, int CO, int KT, int KO>
 hipError_t launch_tailg(const TGArgs& a, hipStream_t st) {
   using C = TG<CO, KT, KO>;
-  static std::once_flag once;
-  static hipError_t attr = hipSuccess;
-  std::call_once(once, [] {
-    attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&tailg_kernel<T, CO, KT, KO>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-  });
+  static LdsOptIn lds_site;
+  const hipError_t attr = allow_lds(
+      lds_site, {reinterpret_cast<const void*>(&tailg_kernel<T, CO, KT, KO>)}, C::LDS_BYTES);
   if (attr != hipSuccess) return attr;
   SPECENH_LAUNCH((tailg_kernel<T, CO, KT, KO>), dim3((unsigned)a.N), dim3(C::THREADS),
                  C::LDS_BYTES, st, a);

@@ -117,6 +117,37 @@ def test_svd_workspace_bounded(batch, m, n, start, stop, path):
         assert sub + eig <= ws <= sub + eig + 8 * batch + 1024
 
 
+def test_svd_workspace_bytes_unchanged():
+    """Both SVD workspace queries return exactly what the library did before the layout
+    arithmetic moved into one place (tests/golden/svd_workspace_bytes.json, recorded by
+    make_golden_svd_workspace.py from a build of the commit it names), over a grid that
+    reaches every layout branch: top-1 with either fallback layout, subspace (direct,
+    complement, with and without the eigen fallback), eigen path, no workspace."""
+    import json
+
+    from specenh import _lib
+
+    L = _lib.lib()
+    gold = json.load(open(os.path.join(REPO, "tests", "golden", "svd_workspace_bytes.json")))
+    assert re.fullmatch(r"[0-9a-f]{40}", gold["commit"])
+    batches = (1, 3, 70000)
+    shapes = ((4, 4), (16, 16), (40, 24), (24, 40), (128, 128), (513, 256), (300, 300))
+    want = {(b, m, n, s, e)
+            for b in batches for m, n in shapes
+            for s, e in ((1, min(m, n)), (0, 4), (0, min(m, n) - 2), (3, 3), (0, min(m, n)),
+                         (2, -1))}
+    rows = gold["denoise_workspace_bytes"]
+    assert {tuple(r[:5]) for r in rows} == want
+    bad = [(r, got) for r in rows
+           if (got := L.specenh_svd_denoise_workspace_bytes(*r[:5])) != r[5]]
+    assert not bad, bad[:5]
+    rows = gold["svd_workspace_bytes"]
+    assert {tuple(r[:3]) for r in rows} == {(b, m, n) for b in batches for m, n in shapes}
+    assert {r[3] for r in rows} >= {1, 4, 16, 40, 41, 256, 300}
+    bad = [(r, got) for r in rows if (got := L.specenh_svd_workspace_bytes(*r[:4])) != r[4]]
+    assert not bad, bad[:5]
+
+
 def test_python_boundary_rejects_cpu_tensors():
     import torch
 
