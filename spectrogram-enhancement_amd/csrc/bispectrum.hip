@@ -12,7 +12,8 @@
 //   by side (all of it fft_lds.hpp, one real frame per N/2-point FFT) and writes 2 X,
 //   unscaled, to the workspace as float2 [shot][signal][frame][F]: frame-major with the bins
 //   contiguous, what the second kernel streams. Every frame of every distinct signal is
-//   transformed exactly once; y or z that alias another signal share its spectra.
+//   transformed exactly once; y or z that alias another signal share its spectra. Its launch
+//   is transform_frames() (stft_plan.hpp), which wavenumber.hip calls too.
 //
 // bispectrum_accumulate_kernel: a workgroup owns one (shot, group, 64 x 64 tile of the plane),
 //   a wave a 32 x 32 quarter of it. Per step of FS frames the workgroup stages the three bin
@@ -58,13 +59,8 @@ constexpr int ROW = 256;  // float2 a staged frame takes: X 64 | Y 64 | Z 127 (+
 static_assert(CHUNK % FS == 0, "a chunk is a whole number of staging steps");
 static_assert(2 * TILE + 2 * TILE - 1 <= ROW && ROW == CT, "one staged element per thread");
 
-struct Signals {
-  const float* p[3];   // distinct signals; shot b of signal s at p[s] + b * stride[s]
-  long long stride[3];
-};
-
 struct TransformArgs {
-  Signals sig;
+  FrameSignals sig;
   int nsig;
   float2* ws;  // [nb][nsig][Tu][F]
   int N, log2n, hop, S, detrend;
@@ -285,6 +281,39 @@ int accumulate(AccumulateArgs g, long long batch, void* bispec, float* bicoh, vo
 }
 
 }  // namespace
+
+// stft_plan.hpp: the transform launches of a call, shots [0, batch) in steps of grid.z
+int transform_frames(const specenh_stft_plan* plan, const FrameSignals& sig, int nsig,
+                     long long batch, long long Tu, void* workspace, hipStream_t stream) {
+  hipError_t e = allow_lds(g_lds, {(const void*)bispectrum_transform_kernel}, MAX_LDS);
+  if (e != hipSuccess)
+    return set_error(SPECENH_EHIP, std::string("bispectrum: ") + hipGetErrorString(e));
+  const int N = plan->nperseg;
+  const long long F = N / 2 + 1;
+  TransformArgs t{};
+  t.sig = sig;
+  t.nsig = nsig;
+  t.N = N; t.log2n = ilog2i(N); t.hop = plan->hop;
+  t.S = slots8_for(N); t.detrend = plan->detrend;
+  t.Tu = (int)Tu;
+  t.win = plan->d_window; t.tw = plan->d_tw_nat;
+  const size_t lds = (size_t)t.S * N * sizeof(float2);  // two buffers of S * N/2
+  const long long ws_shot = (long long)nsig * Tu * F;
+  const long long blocks = (Tu + t.S - 1) / t.S;
+  for (long long b0 = 0; b0 < batch; b0 += 65535) {  // grid.z
+    const long long nb = batch - b0 < 65535 ? batch - b0 : 65535;
+    for (int u = 0; u < nsig; ++u) t.sig.p[u] = sig.p[u] + b0 * sig.stride[u];
+    t.ws = reinterpret_cast<float2*>(workspace) + b0 * ws_shot;
+    SPECENH_LAUNCH(bispectrum_transform_kernel, dim3((unsigned)blocks, (unsigned)nsig, (unsigned)nb),
+                   dim3(CT), lds, stream, t);
+    e = hipGetLastError();
+    if (e != hipSuccess)
+      return set_error(SPECENH_EHIP,
+                       std::string("bispectrum_transform launch: ") + hipGetErrorString(e));
+  }
+  return SPECENH_OK;
+}
+
 }  // namespace specenh
 
 extern "C" {
@@ -328,7 +357,7 @@ int specenh_bispectrum(const specenh_stft_plan* plan, const float* x, const floa
   if (!bispec && !bicoh) return set_error(SPECENH_EINVAL, "no output requested");
   if (batch == 0) return SPECENH_OK;
   // the distinct signals, and which of them y and z are
-  Signals sig{};
+  FrameSignals sig{};
   sig.p[0] = x;
   sig.stride[0] = x_stride;
   int nsig = 1, which[3] = {0, 0, 0};
@@ -351,30 +380,9 @@ int specenh_bispectrum(const specenh_stft_plan* plan, const float* x, const floa
     return set_error(SPECENH_EINVAL, "workspace must be 16-byte aligned");
   if (workspace_bytes < specenh_bispectrum_workspace_bytes(plan, batch, nsig, length, navg))
     return set_error(SPECENH_EINVAL, "workspace too small");
-  hipError_t e = allow_lds(g_lds, {(const void*)bispectrum_transform_kernel}, MAX_LDS);
-  if (e != hipSuccess)
-    return set_error(SPECENH_EHIP, std::string("bispectrum: ") + hipGetErrorString(e));
-  TransformArgs t{};
-  t.sig = sig;
-  t.nsig = nsig;
-  t.N = N; t.log2n = ilog2i(N); t.hop = plan->hop;
-  t.S = slots8_for(N); t.detrend = plan->detrend;
-  t.Tu = (int)s.Tu;
-  t.win = plan->d_window; t.tw = plan->d_tw_nat;
-  const size_t lds = (size_t)t.S * N * sizeof(float2);  // two buffers of S * N/2
+  const int trc = transform_frames(plan, sig, nsig, batch, s.Tu, workspace, (hipStream_t)stream);
+  if (trc != SPECENH_OK) return trc;
   const long long ws_shot = (long long)nsig * s.Tu * F;
-  const long long blocks = (s.Tu + t.S - 1) / t.S;
-  for (long long b0 = 0; b0 < batch; b0 += 65535) {  // grid.z
-    const long long nb = batch - b0 < 65535 ? batch - b0 : 65535;
-    for (int u = 0; u < nsig; ++u) t.sig.p[u] = sig.p[u] + b0 * sig.stride[u];
-    t.ws = reinterpret_cast<float2*>(workspace) + b0 * ws_shot;
-    SPECENH_LAUNCH(bispectrum_transform_kernel, dim3((unsigned)blocks, (unsigned)nsig, (unsigned)nb),
-                   dim3(CT), lds, (hipStream_t)stream, t);
-    e = hipGetLastError();
-    if (e != hipSuccess)
-      return set_error(SPECENH_EHIP,
-                       std::string("bispectrum_transform launch: ") + hipGetErrorString(e));
-  }
   AccumulateArgs g{};
   const float2* ws = reinterpret_cast<const float2*>(workspace);
   g.X = ws;

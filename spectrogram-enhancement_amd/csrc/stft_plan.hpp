@@ -1,7 +1,7 @@
 // stft_plan.hpp — the STFT plan object shared by stft_psd.hip (which creates and destroys
 // it) and stft_complex.hip (complex forward / inverse transforms on the same plan), and the
 // host-side arithmetic on it that the averaging ops share (spectral_mean.hip,
-// spectral_matrix.hip, bispectrum.hip).
+// spectral_matrix.hip, bispectrum.hip, wavenumber.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -50,5 +50,17 @@ inline int frame_split(const specenh_stft_plan* plan, long long length, long lon
   s->ncg = (s->glen + SPECENH_SPECTRAL_CHUNK - 1) / SPECENH_SPECTRAL_CHUNK;
   return SPECENH_OK;
 }
+
+// The distinct signals of a bispectrum or wavenumber-spectrum call: shot b of signal s at
+// p[s] + b * stride[s].
+struct FrameSignals {
+  const float* p[3];
+  long long stride[3];
+};
+// Detrends, windows and transforms frames [0, Tu) of every signal of every shot, once, into
+// `workspace` as float2 [batch][nsig][Tu][F] holding 2 X / sqrt(plan->scale) (defined in
+// bispectrum.hip beside its kernel). SPECENH_OK or a negative error.
+int transform_frames(const specenh_stft_plan* plan, const FrameSignals& sig, int nsig,
+                     long long batch, long long Tu, void* workspace, hipStream_t stream);
 
 }  // namespace specenh

@@ -15,6 +15,9 @@ cross-spectral matrix and coherence matrix of a channel array (every pair in one
 bispectrum and squared bicoherence (three-wave coupling, auto and cross):
   specenh.signal.bicoherence (numpy); specenh.bispectrum.bispectrum, bicoherence,
   bispectrum_from_spectra, summed_bicoherence (device tensors)
+two-point wavenumber-frequency spectrum S(k, f) (dispersion relation from two channels):
+  specenh.signal.wavenumber_spectrum (numpy); specenh.wavenumber.wavenumber_spectrum,
+  wavenumber_spectrum_from_spectra, conditional_spectrum, dispersion (device tensors)
 Device fast paths: specgr_batch, denoise_batch, cross_spectrogram_batch, and
 specenh.autograd (differentiable Conv2D / Conv2DTranspose / MaxPooling2D / BCE).
 Every one of them reaches the HIP kernels through the ``torch.ops.specenh`` operators

@@ -245,6 +245,22 @@ SIGNATURES_BISPECTRUM = {
                                               _c.c_void_p, _c.c_void_p]),
 }
 
+# two-point wavenumber-frequency spectrum S(k, f); must match include/specenh_wavenumber.h
+WAVENUMBER_MIN_NK, WAVENUMBER_MAX_NK = 4, 256
+SIGNATURES_WAVENUMBER = {
+    "specenh_wavenumber_workspace_bytes": (_c.c_size_t, [_c.c_void_p, _c.c_longlong,
+                                                         _c.c_longlong, _c.c_longlong,
+                                                         _c.c_longlong]),
+    "specenh_wavenumber_spectrum": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                               _c.c_longlong, _c.c_longlong, _c.c_longlong,
+                                               _c.c_longlong, _c.c_longlong, _c.c_longlong,
+                                               _c.c_void_p, _c.c_void_p, _c.c_size_t,
+                                               _c.c_void_p]),
+    "specenh_wavenumber_spectra": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_longlong,
+                                              _c.c_longlong, _c.c_longlong, _c.c_longlong,
+                                              _c.c_longlong, _c.c_void_p, _c.c_void_p]),
+}
+
 
 def lib():
     """Load (once) and return the ctypes handle; raise ExtensionNotLoaded on failure."""
@@ -265,7 +281,8 @@ def lib():
         dev_build = bool(os.environ.get("SPECENH_LIB"))
         for name, (res, args) in {**SIGNATURES, **SIGNATURES_STFT_COMPLEX,
                                   **SIGNATURES_SPECTRAL, **SIGNATURES_CSM,
-                                  **SIGNATURES_MODES, **SIGNATURES_BISPECTRUM}.items():
+                                  **SIGNATURES_MODES, **SIGNATURES_BISPECTRUM,
+                                  **SIGNATURES_WAVENUMBER}.items():
             if dev_build and not hasattr(h, name):
                 continue  # an older revision's build for an A/B run (tools/build_rev_lib.sh)
             fn = getattr(h, name)

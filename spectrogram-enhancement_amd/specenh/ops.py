@@ -641,6 +641,132 @@ _op("bispectrum_spectra_out(Tensor X, Tensor? Y, Tensor? Z, int navg, int nbins,
     "Tensor(a!)? bispec, Tensor(b!)? bicoh) -> ()", _bispectrum_spectra_out, lambda *a: None)
 
 
+# ---------------------------------------------------------------- wavenumber-frequency spectrum
+def _wn_nk(nk):
+    nk = int(nk)
+    if nk % 2 or not _lib.WAVENUMBER_MIN_NK <= nk <= _lib.WAVENUMBER_MAX_NK:
+        raise ValueError(f"nk must be even and in [{_lib.WAVENUMBER_MIN_NK}, "
+                         f"{_lib.WAVENUMBER_MAX_NK}], got {nk}")
+    return nk
+
+
+def _wn_check(x, y, nperseg, noverlap, navg):
+    _bispec_check(x, y, None, nperseg, noverlap, navg)
+
+
+def _wn_shape(x, nperseg, noverlap, navg, nk):
+    T = (x.shape[1] - nperseg) // (nperseg - noverlap) + 1
+    return x.shape[0], _sp_groups(T, navg), nperseg // 2 + 1, _wn_nk(nk)
+
+
+def _wn_distinct(x, y):
+    """1 when y is x in pointer and stride, else 2, as specenh_wavenumber_spectrum counts."""
+    return _bispec_distinct(x, y, None)
+
+
+def _wn_need(x, nsig, nperseg, noverlap, window, fs, scaling, detrend, navg):
+    from . import stft
+    plan = stft.get_plan_key(x.device, nperseg, noverlap, window, fs, scaling, detrend, 0.0)
+    B, L = x.shape
+    need = int(_lib.lib().specenh_wavenumber_workspace_bytes(plan.handle, B, nsig, L, int(navg)))
+    if need == 0 and B > 0:
+        _lib.check(_lib.SPECENH_EINVAL, "wavenumber_workspace_bytes")
+    return plan, need
+
+
+def wavenumber_workspace(x, y, nperseg, noverlap, window, fs, scaling, detrend, navg):
+    """A workspace for ``wavenumber_spectrum_out`` on ``x[B, L]`` and ``y`` (uint8, from torch's
+    caching allocator): the spectra of every frame that enters a group of every distinct
+    signal, ``8 B nsignals T F`` bytes."""
+    _wn_check(x, y, nperseg, noverlap, navg)
+    _, need = _wn_need(x, _wn_distinct(x, y), nperseg, noverlap, window, fs, scaling, detrend,
+                       navg)
+    return torch.empty(max(need, 1), dtype=torch.uint8, device=x.device)
+
+
+def _wn_output(skf, shape, device):
+    if (tuple(skf.shape) != shape or skf.dtype != torch.float32 or not skf.is_contiguous()
+            or skf.device != device):
+        raise ValueError(f"skf must be contiguous float32 {shape} on x's device")
+
+
+def _wavenumber_spectrum_out(x, y, nperseg, noverlap, window, fs, scaling, detrend, navg, nk,
+                             skf, workspace):
+    _wn_check(x, y, nperseg, noverlap, navg)
+    shape = _wn_shape(x, nperseg, noverlap, navg, nk)
+    _wn_output(skf, shape, x.device)
+    plan, need = _wn_need(x, _wn_distinct(x, y), nperseg, noverlap, window, fs, scaling, detrend,
+                          navg)
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=x.device)
+    if (workspace.device != x.device or not workspace.is_contiguous()
+            or workspace.numel() * workspace.element_size() < need or workspace.data_ptr() % 16):
+        raise ValueError(f"workspace must be a contiguous, 16-byte aligned buffer of at least "
+                         f"{need} bytes on x's device")
+    B, L = x.shape
+    _lib.check(_lib.lib().specenh_wavenumber_spectrum(
+        plan.handle, _vp(x), _vp(y), B, L, _bispec_stride(x), _bispec_stride(y), int(navg),
+        shape[3], _vp(skf), _vp(workspace), workspace.numel() * workspace.element_size(),
+        _st(x)), "wavenumber_spectrum")
+
+
+def _wavenumber_spectrum(x, y, nperseg, noverlap, window, fs, scaling, detrend, navg, nk):
+    _wn_check(x, y, nperseg, noverlap, navg)
+    skf = torch.empty(_wn_shape(x, nperseg, noverlap, navg, nk), dtype=torch.float32,
+                      device=x.device)
+    _wavenumber_spectrum_out(x, y, nperseg, noverlap, window, fs, scaling, detrend, navg, nk, skf,
+                             None)
+    return skf
+
+
+def _wavenumber_spectrum_fake(x, y, nperseg, noverlap, window, fs, scaling, detrend, navg, nk):
+    return x.new_empty(_wn_shape(x, nperseg, noverlap, navg, nk), dtype=torch.float32)
+
+
+def _wn_spectra_shape(X, Y, navg, nk):
+    for name, v in (("X", X), ("Y", Y)):
+        if v.dim() != 3 or v.dtype != torch.complex64 or not v.is_contiguous():
+            raise ValueError(f"{name} must be contiguous complex64 [batch, frames, F]")
+    if Y.shape != X.shape or Y.device != X.device:
+        raise ValueError("X and Y must have the same shape and device")
+    B, T, F = X.shape
+    if not 1 <= F <= 2049:
+        raise ValueError(f"F must be in [1, 2049], got {F}")
+    if T < 1:
+        raise ValueError("the spectra must hold at least one frame")
+    if navg > T:
+        raise ValueError(f"navg = {navg} exceeds the number of frames ({T})")
+    return B, _sp_groups(T, navg), F, _wn_nk(nk)
+
+
+def _wavenumber_spectra_out(X, Y, navg, nk, skf):
+    shape = _wn_spectra_shape(X, Y, navg, nk)
+    _wn_output(skf, shape, X.device)
+    B, T, F = X.shape
+    _lib.check(_lib.lib().specenh_wavenumber_spectra(
+        _vp(X), _vp(Y), B, T, F, int(navg), shape[3], _vp(skf), _st(X)), "wavenumber_spectra")
+
+
+def _wavenumber_spectra(X, Y, navg, nk):
+    skf = torch.empty(_wn_spectra_shape(X, Y, navg, nk), dtype=torch.float32, device=X.device)
+    _wavenumber_spectra_out(X, Y, navg, nk, skf)
+    return skf
+
+
+def _wavenumber_spectra_fake(X, Y, navg, nk):
+    return X.new_empty(_wn_spectra_shape(X, Y, navg, nk), dtype=torch.float32)
+
+
+_op(f"wavenumber_spectrum(Tensor x, Tensor y, {_SP_ARGS}, int nk) -> Tensor",
+    _wavenumber_spectrum, _wavenumber_spectrum_fake)
+_op(f"wavenumber_spectrum_out(Tensor x, Tensor y, {_SP_ARGS}, int nk, Tensor(a!) skf, "
+    "Tensor(b!)? workspace) -> ()", _wavenumber_spectrum_out, lambda *a: None)
+_op("wavenumber_spectra(Tensor X, Tensor Y, int navg, int nk) -> Tensor", _wavenumber_spectra,
+    _wavenumber_spectra_fake)
+_op("wavenumber_spectra_out(Tensor X, Tensor Y, int navg, int nk, Tensor(a!) skf) -> ()",
+    _wavenumber_spectra_out, lambda *a: None)
+
+
 # ---------------------------------------------------------------- Hermitian eigensolver
 def _eig_check(a, k):
     if a.dtype != torch.complex64 or a.dim() < 2 or a.shape[-1] != a.shape[-2]:

@@ -9,7 +9,9 @@ fused launch of csrc/spectral_mean.hip; ``average='mean'`` only). ``cross_spectr
 (not in scipy) gives ``csd`` / ``coherence`` of every channel pair of an array in one call
 (csrc/spectral_matrix.hip), ``array_modes`` the eigendecomposition of those matrices
 (csrc/herm_eig.hip), ``bicoherence`` (not in scipy) the squared bicoherence of one to three
-signals (csrc/bispectrum.hip). There is no CPU fallback.
+signals (csrc/bispectrum.hip), ``wavenumber_spectrum`` (not in scipy) the two-point
+wavenumber-frequency spectrum ``S(k, f)`` of two channels (csrc/wavenumber.hip). There is no
+CPU fallback.
 
 Differences from scipy, each one an exception rather than another result:
 ``nfft != nperseg``, two-sided spectra, axes other than the defaults, and the ``'even'``,
@@ -25,6 +27,7 @@ import torch
 from . import bispectrum as _bispectrum
 from . import spectral as _spectral
 from . import stft as _stft
+from . import wavenumber as _wavenumber
 
 
 def _upload(t: torch.Tensor) -> torch.Tensor:
@@ -242,3 +245,30 @@ def bicoherence(x, y=None, z=None, fs=1.0, window="hann", nperseg=None, noverlap
                                     noverlap=noverlap, detrend=detrend, nbins=nbins)
     b2 = b2.cpu().numpy().astype(np.float64)
     return f, b2.reshape(lead + b2.shape[1:])
+
+
+def wavenumber_spectrum(x, y, fs=1.0, window="hann", nperseg=None, noverlap=None,
+                        detrend="constant", scaling="density", navg=None, nk=64, dx=1.0):
+    """The two-point wavenumber-frequency spectrum ``S(k, f)`` of two channels ``dx`` apart
+    (Beall, Kim & Powers 1982; not in scipy: one call of
+    ``specenh.wavenumber.wavenumber_spectrum``, csrc/wavenumber.hip): the power-weighted
+    histogram of the per-frame cross-phase of ``y`` relative to ``x`` over ``nk`` centred bins.
+    Returns ``(f, k, t_groups, S)``, ``S`` float64 ``[..., G, F, nk]``; the leading axes are
+    flattened into the batch and restored."""
+    nperseg = 256 if nperseg is None else int(nperseg)
+    arrs = [np.asarray(v) for v in (x, y)]
+    for a in arrs:
+        if np.iscomplexobj(a):
+            raise NotImplementedError("complex input is not supported on the GPU path")
+        if a.ndim == 0:
+            raise ValueError("x must be at least 1-D")
+        if a.shape != arrs[0].shape:
+            raise ValueError("x and y must have the same shape")
+    lead = arrs[0].shape[:-1]
+    ts = [_upload(torch.from_numpy(_leading(np.array(a, dtype=np.float32, order="C"), 1)[0]))
+          for a in arrs]
+    f, k, t, S = _wavenumber.wavenumber_spectrum(
+        ts[0], ts[1], fs=fs, window=window, nperseg=nperseg, noverlap=noverlap, detrend=detrend,
+        scaling=scaling, navg=navg, nk=nk, dx=dx)
+    S = S.cpu().numpy().astype(np.float64)
+    return f, k, t, S.reshape(lead + S.shape[1:])
