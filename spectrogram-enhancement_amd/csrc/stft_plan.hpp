@@ -21,6 +21,8 @@ struct specenh_stft_plan {
   // complex STFT / inverse STFT (stft_complex.hip)
   double win_sum, win_sumsq;  // sum(w), sum(w^2) of the fp64 window
   float2* d_tw_nat;           // W_N^n = exp(-2 pi i n / N), n = 0 .. N-1, natural order
+  // zero-padded frames (correlation.hip): a real 2N-point frame through an N-point transform
+  float2* d_tw_pad;           // W_2N^n = exp(-pi i n / N), n = 0 .. N-1
 };
 
 namespace specenh {

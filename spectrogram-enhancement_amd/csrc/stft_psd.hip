@@ -1440,6 +1440,7 @@ int specenh_stft_plan_create(specenh_stft_plan** plan, int nperseg, int noverlap
   if (e == hipSuccess) e = hipMalloc(&p->d_twiddle, tw.size() * sizeof(float2));
   if (e == hipSuccess) e = hipMalloc(&p->d_dc, N * sizeof(double));
   if (e == hipSuccess) e = hipMalloc(&p->d_tw_nat, N * sizeof(float2));
+  if (e == hipSuccess) e = hipMalloc(&p->d_tw_pad, N * sizeof(float2));
   if (e == hipSuccess) {  // natural-order twiddles of the complex STFT / inverse STFT
     std::vector<float2> nat(N);
     for (int i = 0; i < N; ++i) {
@@ -1447,6 +1448,14 @@ int specenh_stft_plan_create(specenh_stft_plan** plan, int nperseg, int noverlap
       nat[i] = make_float2(float(cs.c), float(-cs.s));
     }
     e = hipMemcpy(p->d_tw_nat, nat.data(), N * sizeof(float2), hipMemcpyHostToDevice);
+  }
+  if (e == hipSuccess) {  // the unpack twiddles of a frame zero-padded to 2N (correlation.hip)
+    std::vector<float2> pad(N);
+    for (int i = 0; i < N; ++i) {
+      ct::CS cs = ct::cossin_frac(i, 2 * N);
+      pad[i] = make_float2(float(cs.c), float(-cs.s));
+    }
+    e = hipMemcpy(p->d_tw_pad, pad.data(), N * sizeof(float2), hipMemcpyHostToDevice);
   }
   if (e == hipSuccess) {
     std::vector<double> dc(N);
@@ -1460,6 +1469,7 @@ int specenh_stft_plan_create(specenh_stft_plan** plan, int nperseg, int noverlap
     (void)hipFree(p->d_twiddle);
     (void)hipFree(p->d_dc);
     (void)hipFree(p->d_tw_nat);
+    (void)hipFree(p->d_tw_pad);
     delete p;
     return set_error(SPECENH_EHIP, std::string("plan allocation: ") + hipGetErrorString(e));
   }
@@ -1473,6 +1483,7 @@ int specenh_stft_plan_destroy(specenh_stft_plan* plan) {
   (void)hipFree(plan->d_twiddle);
   (void)hipFree(plan->d_dc);
   (void)hipFree(plan->d_tw_nat);
+  (void)hipFree(plan->d_tw_pad);
   delete plan;
   return SPECENH_OK;
 }

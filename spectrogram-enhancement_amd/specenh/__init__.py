@@ -18,6 +18,9 @@ bispectrum and squared bicoherence (three-wave coupling, auto and cross):
 two-point wavenumber-frequency spectrum S(k, f) (dispersion relation from two channels):
   specenh.signal.wavenumber_spectrum (numpy); specenh.wavenumber.wavenumber_spectrum,
   wavenumber_spectrum_from_spectra, conditional_spectrum, dispersion (device tensors)
+block-averaged lagged cross-correlation (time-delay estimation, correlation time):
+  specenh.signal.correlate (numpy); specenh.correlation.correlate, autocorrelate,
+  correlation_lags, time_delay, correlation_time (device tensors)
 Device fast paths: specgr_batch, denoise_batch, cross_spectrogram_batch, and
 specenh.autograd (differentiable Conv2D / Conv2DTranspose / MaxPooling2D / BCE).
 Every one of them reaches the HIP kernels through the ``torch.ops.specenh`` operators

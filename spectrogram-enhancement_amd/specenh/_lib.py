@@ -261,6 +261,19 @@ SIGNATURES_WAVENUMBER = {
                                               _c.c_longlong, _c.c_void_p, _c.c_void_p]),
 }
 
+# block-averaged cross-correlation; must match include/specenh_correlation.h
+CORR_RAW, CORR_COEFF = 0, 1  # SPECENH_CORR_RAW, SPECENH_CORR_COEFF
+CORR_MAX_NPERSEG = 2048  # the padded transform is at most the 4096 points of the LDS FFT
+SIGNATURES_CORRELATION = {
+    "specenh_correlation_workspace_bytes": (_c.c_size_t, [_c.c_void_p, _c.c_longlong,
+                                                          _c.c_longlong, _c.c_longlong,
+                                                          _c.c_longlong]),
+    "specenh_correlation": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_longlong,
+                                       _c.c_longlong, _c.c_longlong, _c.c_longlong,
+                                       _c.c_longlong, _c.c_longlong, _c.c_int, _c.c_void_p,
+                                       _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+}
+
 
 def lib():
     """Load (once) and return the ctypes handle; raise ExtensionNotLoaded on failure."""
@@ -282,7 +295,7 @@ def lib():
         for name, (res, args) in {**SIGNATURES, **SIGNATURES_STFT_COMPLEX,
                                   **SIGNATURES_SPECTRAL, **SIGNATURES_CSM,
                                   **SIGNATURES_MODES, **SIGNATURES_BISPECTRUM,
-                                  **SIGNATURES_WAVENUMBER}.items():
+                                  **SIGNATURES_WAVENUMBER, **SIGNATURES_CORRELATION}.items():
             if dev_build and not hasattr(h, name):
                 continue  # an older revision's build for an A/B run (tools/build_rev_lib.sh)
             fn = getattr(h, name)

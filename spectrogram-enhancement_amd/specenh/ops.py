@@ -767,6 +767,92 @@ _op("wavenumber_spectra_out(Tensor X, Tensor Y, int navg, int nk, Tensor(a!) skf
     _wavenumber_spectra_out, lambda *a: None)
 
 
+# ---------------------------------------------------------------- block-averaged correlation
+def _corr_check(x, y, nperseg, noverlap, navg, maxlag, mode):
+    if nperseg == 4096:
+        raise NotImplementedError("correlation: nperseg = 4096 is not supported (the padded "
+                                  "transform would be 8192 points); nperseg must be a power of "
+                                  "two in [64, 2048]")
+    if nperseg < 64 or nperseg > _lib.CORR_MAX_NPERSEG or nperseg & (nperseg - 1):
+        raise NotImplementedError("correlation: nperseg must be a power of two in [64, 2048]")
+    if not 0 <= maxlag < nperseg:
+        raise ValueError(f"maxlag must be in [0, nperseg - 1], got {maxlag}")
+    if mode not in (_lib.CORR_RAW, _lib.CORR_COEFF):
+        raise ValueError(f"mode must be {_lib.CORR_RAW} (raw) or {_lib.CORR_COEFF} (coeff)")
+    _bispec_check(x, y, None, nperseg, noverlap, navg)
+
+
+def _corr_shape(x, nperseg, noverlap, navg, maxlag):
+    T = (x.shape[1] - nperseg) // (nperseg - noverlap) + 1
+    return x.shape[0], _sp_groups(T, navg), 2 * int(maxlag) + 1
+
+
+def _corr_need(x, nperseg, noverlap, window, fs, scaling, detrend, navg, maxlag):
+    from . import stft
+    plan = stft.get_plan_key(x.device, nperseg, noverlap, window, fs, scaling, detrend, 0.0)
+    B, L = x.shape
+    return plan, int(_lib.lib().specenh_correlation_workspace_bytes(plan.handle, B, L, int(navg),
+                                                                    int(maxlag)))
+
+
+def correlation_workspace(x, y, nperseg, noverlap, window, fs, scaling, detrend, navg, maxlag):
+    """A workspace for ``correlation_out`` on ``x[B, L]`` and ``y`` (uint8, from torch's caching
+    allocator; one byte when none is needed): one record of ``8 (nperseg + 3)`` bytes per chunk
+    of 32 frames when a group is longer than a chunk."""
+    _corr_check(x, y, nperseg, noverlap, navg, maxlag, _lib.CORR_RAW)
+    _, need = _corr_need(x, nperseg, noverlap, window, fs, scaling, detrend, navg, maxlag)
+    return torch.empty(max(need, 1), dtype=torch.uint8, device=x.device)
+
+
+def _correlation_out(x, y, nperseg, noverlap, window, fs, scaling, detrend, navg, maxlag, mode,
+                     out, energies, workspace):
+    _corr_check(x, y, nperseg, noverlap, navg, maxlag, mode)
+    shape = _corr_shape(x, nperseg, noverlap, navg, maxlag)
+    for o, sh, name in ((out, shape, "out"), (energies, shape[:2] + (2,), "energies")):
+        if o is not None and (tuple(o.shape) != sh or o.dtype != torch.float32
+                              or not o.is_contiguous() or o.device != x.device):
+            raise ValueError(f"{name} must be contiguous float32 {sh} on x's device")
+    plan, need = _corr_need(x, nperseg, noverlap, window, fs, scaling, detrend, navg, maxlag)
+    if need and workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
+    if need and (workspace.device != x.device or not workspace.is_contiguous()
+                 or workspace.numel() * workspace.element_size() < need
+                 or workspace.data_ptr() % 16):
+        raise ValueError(f"workspace must be a contiguous, 16-byte aligned buffer of at least "
+                         f"{need} bytes on x's device")
+    B, L = x.shape
+    _lib.check(_lib.lib().specenh_correlation(
+        plan.handle, _vp(x), _vp(y), B, L, _bispec_stride(x), _bispec_stride(y), int(navg),
+        int(maxlag), int(mode), _vp(out), _vp(energies), _vp(workspace if need else None),
+        workspace.numel() * workspace.element_size() if need else 0, _st(x)), "correlation")
+
+
+def _correlation(x, y, nperseg, noverlap, window, fs, scaling, detrend, navg, maxlag, mode):
+    _corr_check(x, y, nperseg, noverlap, navg, maxlag, mode)
+    shape = _corr_shape(x, nperseg, noverlap, navg, maxlag)
+    out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    energies = torch.empty(shape[:2] + (2,), dtype=torch.float32, device=x.device)
+    _correlation_out(x, y, nperseg, noverlap, window, fs, scaling, detrend, navg, maxlag, mode,
+                     out, energies, None)
+    return out, energies
+
+
+def _correlation_fake(x, y, nperseg, noverlap, window, fs, scaling, detrend, navg, maxlag, mode):
+    _corr_check(x, y, nperseg, noverlap, navg, maxlag, mode)
+    shape = _corr_shape(x, nperseg, noverlap, navg, maxlag)
+    return (x.new_empty(shape, dtype=torch.float32),
+            x.new_empty(shape[:2] + (2,), dtype=torch.float32))
+
+
+# the schema calls the mode `normalize`: torch's functionalisation of a mutable operator passes
+# a keyword `mode` of its own
+_op(f"correlation(Tensor x, Tensor y, {_SP_ARGS}, int maxlag, int normalize) -> "
+    "(Tensor, Tensor)", _correlation, _correlation_fake)
+_op(f"correlation_out(Tensor x, Tensor y, {_SP_ARGS}, int maxlag, int normalize, "
+    "Tensor(a!) out, Tensor(b!)? energies, Tensor(c!)? workspace) -> ()", _correlation_out,
+    lambda *a: None)
+
+
 # ---------------------------------------------------------------- Hermitian eigensolver
 def _eig_check(a, k):
     if a.dtype != torch.complex64 or a.dim() < 2 or a.shape[-1] != a.shape[-2]:

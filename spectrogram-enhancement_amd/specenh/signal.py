@@ -10,8 +10,9 @@ fused launch of csrc/spectral_mean.hip; ``average='mean'`` only). ``cross_spectr
 (csrc/spectral_matrix.hip), ``array_modes`` the eigendecomposition of those matrices
 (csrc/herm_eig.hip), ``bicoherence`` (not in scipy) the squared bicoherence of one to three
 signals (csrc/bispectrum.hip), ``wavenumber_spectrum`` (not in scipy) the two-point
-wavenumber-frequency spectrum ``S(k, f)`` of two channels (csrc/wavenumber.hip). There is no
-CPU fallback.
+wavenumber-frequency spectrum ``S(k, f)`` of two channels (csrc/wavenumber.hip), ``correlate``
+the block-averaged lagged cross-correlation of two channels (csrc/correlation.hip; per frame
+``scipy.signal.correlate(y_t, x_t)``). There is no CPU fallback.
 
 Differences from scipy, each one an exception rather than another result:
 ``nfft != nperseg``, two-sided spectra, axes other than the defaults, and the ``'even'``,
@@ -25,6 +26,7 @@ import numpy as np
 import torch
 
 from . import bispectrum as _bispectrum
+from . import correlation as _correlation
 from . import spectral as _spectral
 from . import stft as _stft
 from . import wavenumber as _wavenumber
@@ -272,3 +274,31 @@ def wavenumber_spectrum(x, y, fs=1.0, window="hann", nperseg=None, noverlap=None
         scaling=scaling, navg=navg, nk=nk, dx=dx)
     S = S.cpu().numpy().astype(np.float64)
     return f, k, t, S.reshape(lead + S.shape[1:])
+
+
+def correlate(x, y, window="boxcar", nperseg=None, noverlap=None, detrend="constant", navg=None,
+              maxlag=None, normalize="coeff", unbiased=False, fs=1.0):
+    """The block-averaged lagged cross-correlation of two channels (one call of
+    ``specenh.correlation.correlate``, csrc/correlation.hip): per frame
+    ``scipy.signal.correlate(y_t, x_t, 'full')[N - 1 + m]`` of the detrended, windowed frames,
+    averaged over each group, as the coefficient (``normalize="coeff"``) or raw. A positive lag
+    means ``y`` lags ``x``. Returns ``(lags, t_groups, R)``, ``lags`` in seconds, ``R`` float64
+    ``[..., G, 2 maxlag + 1]``; the leading axes are flattened into the batch and restored."""
+    nperseg = 256 if nperseg is None else int(nperseg)
+    arrs = [np.asarray(v) for v in (x, y)]
+    for a in arrs:
+        if np.iscomplexobj(a):
+            raise NotImplementedError("complex input is not supported on the GPU path")
+        if a.ndim == 0:
+            raise ValueError("x must be at least 1-D")
+        if a.shape != arrs[0].shape:
+            raise ValueError("x and y must have the same shape")
+    lead = arrs[0].shape[:-1]
+    tx = _upload(torch.from_numpy(_leading(np.array(arrs[0], dtype=np.float32, order="C"), 1)[0]))
+    ty = tx if y is x else _upload(
+        torch.from_numpy(_leading(np.array(arrs[1], dtype=np.float32, order="C"), 1)[0]))
+    lags, t, R = _correlation.correlate(
+        tx, ty, window=window, nperseg=nperseg, noverlap=noverlap, detrend=detrend, navg=navg,
+        maxlag=maxlag, normalize=normalize, unbiased=unbiased, fs=fs)
+    R = R.cpu().numpy().astype(np.float64)
+    return lags, t, R.reshape(lead + R.shape[1:])
