@@ -13,7 +13,7 @@
 //   unscaled, to the workspace as float2 [shot][signal][frame][F]: frame-major with the bins
 //   contiguous, what the second kernel streams. Every frame of every distinct signal is
 //   transformed exactly once; y or z that alias another signal share its spectra. Its launch
-//   is transform_frames() (stft_plan.hpp), which wavenumber.hip calls too.
+//   is transform_frames() (averaging.hpp), which wavenumber.hip calls too.
 //
 // bispectrum_accumulate_kernel: a workgroup owns one (shot, group, 64 x 64 tile of the plane),
 //   a wave a 32 x 32 quarter of it. Per step of FS frames the workgroup stages the three bin
@@ -41,7 +41,7 @@
 
 #include "specenh_bispectrum.h"
 #include "runtime.hpp"
-#include "stft_plan.hpp"
+#include "averaging.hpp"
 #include "fft_lds.hpp"
 
 namespace specenh {
@@ -250,13 +250,6 @@ __global__ __launch_bounds__(CT) void bispectrum_accumulate_kernel(AccumulateArg
 
 LdsOptIn g_lds;  // N >= 1024 takes 64 KiB of dynamic LDS next to the static stat[]
 
-// the split of a call, or a negative error; validates everything but the pointers
-int split_for(const specenh_stft_plan* plan, long long batch, long long length, long long navg,
-              FrameSplit* s) {
-  if (batch < 0) return set_error(SPECENH_EINVAL, "batch must be >= 0");
-  return frame_split(plan, length, navg, true, s);
-}
-
 // the accumulate launches of a call: shots [0, batch) in steps of grid.y
 int accumulate(AccumulateArgs g, long long batch, void* bispec, float* bicoh, void* stream) {
   const long long per_shot = (long long)g.G * g.nt * g.nt;
@@ -272,17 +265,14 @@ int accumulate(AccumulateArgs g, long long batch, void* bispec, float* bicoh, vo
     g.coh = bicoh ? bicoh + b0 * out_shot : nullptr;
     SPECENH_LAUNCH(bispectrum_accumulate_kernel, dim3((unsigned)per_shot, (unsigned)nb),
                    dim3(CT), 0, (hipStream_t)stream, g);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-      return set_error(SPECENH_EHIP,
-                       std::string("bispectrum_accumulate launch: ") + hipGetErrorString(e));
+    if (int rc = launched("bispectrum_accumulate")) return rc;
   }
   return SPECENH_OK;
 }
 
 }  // namespace
 
-// stft_plan.hpp: the transform launches of a call, shots [0, batch) in steps of grid.z
+// averaging.hpp: the transform launches of a call, shots [0, batch) in steps of grid.z
 int transform_frames(const specenh_stft_plan* plan, const FrameSignals& sig, int nsig,
                      long long batch, long long Tu, void* workspace, hipStream_t stream) {
   hipError_t e = allow_lds(g_lds, {(const void*)bispectrum_transform_kernel}, MAX_LDS);
@@ -306,10 +296,7 @@ int transform_frames(const specenh_stft_plan* plan, const FrameSignals& sig, int
     t.ws = reinterpret_cast<float2*>(workspace) + b0 * ws_shot;
     SPECENH_LAUNCH(bispectrum_transform_kernel, dim3((unsigned)blocks, (unsigned)nsig, (unsigned)nb),
                    dim3(CT), lds, stream, t);
-    e = hipGetLastError();
-    if (e != hipSuccess)
-      return set_error(SPECENH_EHIP,
-                       std::string("bispectrum_transform launch: ") + hipGetErrorString(e));
+    if (int rc = launched("bispectrum_transform")) return rc;
   }
   return SPECENH_OK;
 }
@@ -323,17 +310,12 @@ size_t specenh_bispectrum_workspace_bytes(const specenh_stft_plan* plan, long lo
                                           long long navg) {
   using namespace specenh;
   FrameSplit s;
-  if (!plan) {
-    set_error(SPECENH_EINVAL, "null plan");
-    return 0;
-  }
+  if (check_call(plan, batch, length, navg, true, &s) != SPECENH_OK) return 0;
   if (nsignals < 1 || nsignals > 3) {
     set_error(SPECENH_EINVAL, "nsignals must be in [1, 3]");
     return 0;
   }
-  if (split_for(plan, batch, length, navg, &s) != SPECENH_OK) return 0;
-  return (size_t)batch * (size_t)nsignals * (size_t)s.Tu * (size_t)(plan->nperseg / 2 + 1) * 2 *
-         sizeof(float);
+  return frames_workspace_bytes(plan, batch, nsignals, s.Tu);
 }
 
 int specenh_bispectrum(const specenh_stft_plan* plan, const float* x, const float* y,
@@ -342,14 +324,12 @@ int specenh_bispectrum(const specenh_stft_plan* plan, const float* x, const floa
                        void* bispec, float* bicoh, void* workspace, size_t workspace_bytes,
                        void* stream) {
   using namespace specenh;
-  if (!plan) return set_error(SPECENH_EINVAL, "null plan");
   if (!x) return set_error(SPECENH_EINVAL, "null x");
   FrameSplit s;
-  const int rc = split_for(plan, batch, length, navg, &s);
-  if (rc != SPECENH_OK) return rc;
-  if (x_stride < length) return set_error(SPECENH_EINVAL, "x_stride < length");
-  if (y && y_stride < length) return set_error(SPECENH_EINVAL, "y_stride < length");
-  if (z && z_stride < length) return set_error(SPECENH_EINVAL, "z_stride < length");
+  if (int rc = check_call(plan, batch, length, navg, true, &s)) return rc;
+  const SignalArg in[] = {{x, x_stride, "x_stride < length"}, {y, y_stride, "y_stride < length"},
+                          {z, z_stride, "z_stride < length"}};
+  if (int rc = check_strides(in, 3, length)) return rc;
   const int N = plan->nperseg;
   const long long F = N / 2 + 1;
   if (nbins <= 0) nbins = F;
@@ -358,30 +338,13 @@ int specenh_bispectrum(const specenh_stft_plan* plan, const float* x, const floa
   if (batch == 0) return SPECENH_OK;
   // the distinct signals, and which of them y and z are
   FrameSignals sig{};
-  sig.p[0] = x;
-  sig.stride[0] = x_stride;
-  int nsig = 1, which[3] = {0, 0, 0};
-  const float* ptr[3] = {x, y, z};
-  const long long str[3] = {x_stride, y_stride, z_stride};
-  for (int v = 1; v < 3; ++v) {
-    if (!ptr[v]) continue;  // aliases x
-    int found = -1;
-    for (int u = 0; u < nsig; ++u)
-      if (sig.p[u] == ptr[v] && sig.stride[u] == str[v]) found = u;
-    if (found < 0) {
-      sig.p[nsig] = ptr[v];
-      sig.stride[nsig] = str[v];
-      found = nsig++;
-    }
-    which[v] = found;
-  }
-  if (!workspace) return set_error(SPECENH_EINVAL, "null workspace");
-  if (reinterpret_cast<size_t>(workspace) % 16)
-    return set_error(SPECENH_EINVAL, "workspace must be 16-byte aligned");
-  if (workspace_bytes < specenh_bispectrum_workspace_bytes(plan, batch, nsig, length, navg))
-    return set_error(SPECENH_EINVAL, "workspace too small");
-  const int trc = transform_frames(plan, sig, nsig, batch, s.Tu, workspace, (hipStream_t)stream);
-  if (trc != SPECENH_OK) return trc;
+  int which[3];
+  const int nsig = collect_signals(in, 3, &sig, which);
+  if (int rc = check_workspace(workspace, workspace_bytes,
+                               frames_workspace_bytes(plan, batch, nsig, s.Tu)))
+    return rc;
+  if (int rc = transform_frames(plan, sig, nsig, batch, s.Tu, workspace, (hipStream_t)stream))
+    return rc;
   const long long ws_shot = (long long)nsig * s.Tu * F;
   AccumulateArgs g{};
   const float2* ws = reinterpret_cast<const float2*>(workspace);
@@ -402,11 +365,8 @@ int specenh_bispectrum_spectra(const void* X, const void* Y, const void* Z, long
                                long long nbins, void* bispec, float* bicoh, void* stream) {
   using namespace specenh;
   if (!X) return set_error(SPECENH_EINVAL, "null X");
-  if (batch < 0) return set_error(SPECENH_EINVAL, "batch must be >= 0");
-  if (nfreq < 1 || nfreq > 2049) return set_error(SPECENH_EINVAL, "nfreq must be in [1, 2049]");
-  if (frames > (1ll << 30)) return set_error(SPECENH_EINVAL, "too many frames");
-  const long long G = specenh_spectral_groups(frames, navg);
-  if (G < 0) return (int)G;
+  long long G;
+  if (int rc = check_spectra(batch, frames, nfreq, navg, &G)) return rc;
   if (nbins <= 0) nbins = nfreq;
   if (nbins > nfreq) return set_error(SPECENH_EINVAL, "nbins must be in [1, nfreq]");
   if (!bispec && !bicoh) return set_error(SPECENH_EINVAL, "no output requested");

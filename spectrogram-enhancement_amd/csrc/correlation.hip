@@ -38,7 +38,7 @@
 
 #include "specenh_correlation.h"
 #include "runtime.hpp"
-#include "stft_plan.hpp"
+#include "averaging.hpp"
 #include "fft_lds.hpp"
 
 namespace specenh {
@@ -48,9 +48,6 @@ constexpr int CT = 256;  // threads per workgroup
 constexpr int CHUNK = SPECENH_SPECTRAL_CHUNK;
 constexpr int MAX_LDS = 64 * 1024;
 constexpr int MAX_N = 2048;  // the padded transform is at most the 4096 points of the LDS FFT
-
-// N-point complex transforms side by side: 512 radix-4 butterflies a pass, at least x and y.
-inline int slots_for(int N) { return N >= 1024 ? 2 : 2048 / N; }
 
 using namespace fft_lds;  // load_frames, stockham, unpack2, nyquist2, c_mul
 
@@ -244,10 +241,10 @@ ChunkKernel chunk_kernel(int N, bool pair) {
 // N = 2048 takes 64 KiB of dynamic LDS next to the static stat[] and esum[]
 LdsOptIn g_lds;
 
-// nperseg, maxlag and the frame split of a call; SPECENH_OK or a negative error
-int check_call(const specenh_stft_plan* plan, long long length, long long navg, long long maxlag,
-               FrameSplit* s) {
-  const int N = plan->nperseg;
+// plan, batch, nperseg, the frame split and maxlag of a call; SPECENH_OK or a negative error
+int check_lags(const specenh_stft_plan* plan, long long batch, long long length, long long navg,
+               long long maxlag, FrameSplit* s) {
+  const int N = plan ? plan->nperseg : 64;  // its own nperseg range, ahead of frame_split's
   if (N == 4096)
     return set_error(SPECENH_EUNSUPPORTED,
                      "correlation: nperseg = 4096 is not supported (the padded transform would "
@@ -255,8 +252,7 @@ int check_call(const specenh_stft_plan* plan, long long length, long long navg, 
   if (N < 64 || N > MAX_N || (N & (N - 1)))
     return set_error(SPECENH_EUNSUPPORTED,
                      "correlation: nperseg must be a power of two in [64, 2048]");
-  const int rc = frame_split(plan, length, navg, true, s);
-  if (rc != SPECENH_OK) return rc;
+  if (int rc = check_call(plan, batch, length, navg, true, s)) return rc;
   if (maxlag < 0 || maxlag >= N)
     return set_error(SPECENH_EINVAL, "maxlag must be in [0, nperseg - 1]");
   return SPECENH_OK;
@@ -273,11 +269,7 @@ size_t specenh_correlation_workspace_bytes(const specenh_stft_plan* plan, long l
                                            long long length, long long navg, long long maxlag) {
   using namespace specenh;
   FrameSplit s;
-  if (!plan || batch < 0) {
-    set_error(SPECENH_EINVAL, plan ? "batch must be >= 0" : "null plan");
-    return 0;
-  }
-  if (check_call(plan, length, navg, maxlag, &s) != SPECENH_OK || s.ncg == 1) return 0;
+  if (check_lags(plan, batch, length, navg, maxlag, &s) != SPECENH_OK || s.ncg == 1) return 0;
   return (size_t)batch * s.G * s.ncg * record_bytes(plan->nperseg);
 }
 
@@ -287,29 +279,25 @@ int specenh_correlation(const specenh_stft_plan* plan, const float* x, const flo
                         float* out, float* energies, void* workspace, size_t workspace_bytes,
                         void* stream) {
   using namespace specenh;
-  if (!plan) return set_error(SPECENH_EINVAL, "null plan");
   if (!x) return set_error(SPECENH_EINVAL, "null x");
   if (!y) return set_error(SPECENH_EINVAL, "null y");
-  if (batch < 0) return set_error(SPECENH_EINVAL, "batch must be >= 0");
   FrameSplit s;
-  const int rc = check_call(plan, length, navg, maxlag, &s);
-  if (rc != SPECENH_OK) return rc;
-  if (x_stride < length) return set_error(SPECENH_EINVAL, "x_stride < length");
-  if (y_stride < length) return set_error(SPECENH_EINVAL, "y_stride < length");
+  if (int rc = check_lags(plan, batch, length, navg, maxlag, &s)) return rc;
+  const SignalArg in[] = {{x, x_stride, "x_stride < length"}, {y, y_stride, "y_stride < length"}};
+  if (int rc = check_strides(in, 2, length)) return rc;
   if (mode != SPECENH_CORR_RAW && mode != SPECENH_CORR_COEFF)
     return set_error(SPECENH_EINVAL, "mode must be SPECENH_CORR_RAW or SPECENH_CORR_COEFF");
   if (!out) return set_error(SPECENH_EINVAL, "null out");
   if (batch == 0) return SPECENH_OK;
   const int N = plan->nperseg;
   if (s.G * s.ncg > 2147483647LL) return set_error(SPECENH_EUNSUPPORTED, "too many chunks");
-  if (s.ncg > 1) {
-    if (!workspace) return set_error(SPECENH_EINVAL, "null workspace");
-    if (reinterpret_cast<size_t>(workspace) % 16)
-      return set_error(SPECENH_EINVAL, "workspace must be 16-byte aligned");
-    if (workspace_bytes < (size_t)batch * s.G * s.ncg * record_bytes(N))
-      return set_error(SPECENH_EINVAL, "workspace too small");
-  }
-  const bool pair = y != x || y_stride != x_stride;  // y given as x: loaded and transformed once
+  if (s.ncg > 1)
+    if (int rc = check_workspace(workspace, workspace_bytes,
+                                 (size_t)batch * s.G * s.ncg * record_bytes(N)))
+      return rc;
+  FrameSignals sig{};
+  int which[2];
+  const bool pair = collect_signals(in, 2, &sig, which) == 2;  // y given as x: loaded once
   hipError_t e = allow_lds(g_lds,
                            {(const void*)chunk_kernel(1024, false), (const void*)chunk_kernel(1024, true),
                             (const void*)chunk_kernel(2048, false), (const void*)chunk_kernel(2048, true)},
@@ -332,18 +320,12 @@ int specenh_correlation(const specenh_stft_plan* plan, const float* x, const flo
     a.out = out + b0 * s.G * (2 * maxlag + 1);
     a.energies = energies ? energies + b0 * s.G * 2 : nullptr;
     a.ws = s.ncg > 1 ? reinterpret_cast<float2*>(workspace) + b0 * s.G * s.ncg * (N + 3) : nullptr;
-    note_launch(reinterpret_cast<const void*>(kern));
-    hipLaunchKernelGGL(kern, dim3((unsigned)(s.G * s.ncg), (unsigned)nb), dim3(CT), lds,
-                       (hipStream_t)stream, a);
-    e = hipGetLastError();
-    if (e != hipSuccess)
-      return set_error(SPECENH_EHIP, std::string("correlation_chunk launch: ") + hipGetErrorString(e));
+    launch(kern, dim3((unsigned)(s.G * s.ncg), (unsigned)nb), dim3(CT), lds, stream, a);
+    if (int rc = launched("correlation_chunk")) return rc;
     if (s.ncg == 1) continue;
     SPECENH_LAUNCH(correlation_fold_kernel, dim3((unsigned)s.G, (unsigned)nb), dim3(CT),
                    (size_t)(2 * N + 1) * sizeof(float2), (hipStream_t)stream, a);
-    e = hipGetLastError();
-    if (e != hipSuccess)
-      return set_error(SPECENH_EHIP, std::string("correlation_fold launch: ") + hipGetErrorString(e));
+    if (int rc = launched("correlation_fold")) return rc;
   }
   return SPECENH_OK;
 }

@@ -40,7 +40,7 @@
 
 #include "specenh_csm.h"
 #include "runtime.hpp"
-#include "stft_plan.hpp"
+#include "averaging.hpp"
 #include "fft_lds.hpp"
 
 namespace specenh {
@@ -226,10 +226,10 @@ LdsOptIn g_lds;  // N >= 1024 takes 64 KiB of dynamic LDS next to the static sta
 // the split of a call, or a negative error; validates everything but the pointers
 int split_for(const specenh_stft_plan* plan, long long batch, long long channels,
               long long length, long long navg, FrameSplit* s) {
-  if (batch < 0) return set_error(SPECENH_EINVAL, "batch must be >= 0");
+  if (int rc = check_call(plan, batch, length, navg, true, s)) return rc;
   if (channels < 2 || channels > SPECENH_CSM_MAX_CHANNELS)
     return set_error(SPECENH_EINVAL, "channels must be in [2, 64]");
-  return frame_split(plan, length, navg, true, s);
+  return SPECENH_OK;
 }
 
 }  // namespace
@@ -241,10 +241,6 @@ size_t specenh_csm_workspace_bytes(const specenh_stft_plan* plan, long long batc
                                    long long channels, long long length, long long navg) {
   using namespace specenh;
   FrameSplit s;
-  if (!plan) {
-    set_error(SPECENH_EINVAL, "null plan");
-    return 0;
-  }
   if (split_for(plan, batch, channels, length, navg, &s) != SPECENH_OK) return 0;
   return (size_t)batch * (size_t)(plan->nperseg / 2 + 1) * (size_t)s.Tu * 2 * (size_t)channels *
          sizeof(float);
@@ -255,23 +251,19 @@ int specenh_csm(const specenh_stft_plan* plan, const float* x, long long batch,
                 long long batch_stride, long long navg, void* csm, float* coh, void* workspace,
                 size_t workspace_bytes, void* stream) {
   using namespace specenh;
-  if (!plan) return set_error(SPECENH_EINVAL, "null plan");
   if (!x) return set_error(SPECENH_EINVAL, "null x");
   FrameSplit s;
-  const int rc = split_for(plan, batch, channels, length, navg, &s);
-  if (rc != SPECENH_OK) return rc;
-  if (channel_stride < length) return set_error(SPECENH_EINVAL, "channel_stride < length");
+  if (int rc = split_for(plan, batch, channels, length, navg, &s)) return rc;
+  if (int rc = check_stride(channel_stride, length, "channel_stride < length")) return rc;
   if (batch_stride < channels * channel_stride)
     return set_error(SPECENH_EINVAL, "batch_stride < channels * channel_stride");
   if (!csm && !coh) return set_error(SPECENH_EINVAL, "no output requested");
   if (batch == 0) return SPECENH_OK;
   const int N = plan->nperseg, C = (int)channels;
   const long long F = N / 2 + 1;
-  if (!workspace) return set_error(SPECENH_EINVAL, "null workspace");
-  if (reinterpret_cast<size_t>(workspace) % 16)
-    return set_error(SPECENH_EINVAL, "workspace must be 16-byte aligned");
-  if (workspace_bytes < specenh_csm_workspace_bytes(plan, batch, channels, length, navg))
-    return set_error(SPECENH_EINVAL, "workspace too small");
+  if (int rc = check_workspace(workspace, workspace_bytes,
+                               specenh_csm_workspace_bytes(plan, batch, channels, length, navg)))
+    return rc;
   const int ntp = C <= TILE ? 1 : 3;
   const long long per_shot = s.G * F * ntp;  // waves of the Gram kernel
   if (per_shot > (1ll << 31)) return set_error(SPECENH_EUNSUPPORTED, "too many groups");
@@ -301,18 +293,14 @@ int specenh_csm(const specenh_stft_plan* plan, const float* x, long long batch,
     SPECENH_LAUNCH(csm_transform_kernel,
                    dim3((unsigned)(s.Tu * t.nblk), 1, (unsigned)nb), dim3(CT),
                    lds, (hipStream_t)stream, t);
-    e = hipGetLastError();
-    if (e != hipSuccess)
-      return set_error(SPECENH_EHIP, std::string("csm_transform launch: ") + hipGetErrorString(e));
+    if (int rc = launched("csm_transform")) return rc;
     g.ws = t.ws;
     g.csm = csm ? reinterpret_cast<float2*>(csm) + b0 * out_shot : nullptr;
     g.coh = coh ? coh + b0 * out_shot : nullptr;
     g.waves = nb * per_shot;
     const long long blocks = (g.waves + CT / 64 - 1) / (CT / 64);
     SPECENH_LAUNCH(csm_gram_kernel, dim3((unsigned)blocks), dim3(CT), 0, (hipStream_t)stream, g);
-    e = hipGetLastError();
-    if (e != hipSuccess)
-      return set_error(SPECENH_EHIP, std::string("csm_gram launch: ") + hipGetErrorString(e));
+    if (int rc = launched("csm_gram")) return rc;
   }
   return SPECENH_OK;
 }

@@ -27,7 +27,7 @@
 
 #include "specenh_spectral.h"
 #include "runtime.hpp"
-#include "stft_plan.hpp"
+#include "averaging.hpp"
 #include "fft_lds.hpp"
 
 namespace specenh {
@@ -41,9 +41,6 @@ constexpr int CT = 256;  // threads per workgroup
 // read, an eighth at hop = N/4.
 constexpr int CHUNK = SPECENH_SPECTRAL_CHUNK;
 constexpr int MAX_LDS = 64 * 1024;
-
-// Transforms side by side: 256 radix-4 butterflies a pass where N allows, at least x and y.
-inline int slots_for(int N) { return N >= 1024 ? 2 : 2048 / N; }
 
 using namespace fft_lds;  // load_frames, stockham, unpack2, nyquist2
 
@@ -239,11 +236,7 @@ size_t specenh_spectral_workspace_bytes(const specenh_stft_plan* plan, long long
                                         long long length, long long navg) {
   using namespace specenh;
   FrameSplit s;
-  if (!plan || batch < 0) {
-    set_error(SPECENH_EINVAL, plan ? "batch must be >= 0" : "null plan");
-    return 0;
-  }
-  if (frame_split(plan, length, navg, false, &s) != SPECENH_OK || s.ncg == 1) return 0;
+  if (check_call(plan, batch, length, navg, false, &s) != SPECENH_OK || s.ncg == 1) return 0;
   return (size_t)batch * s.G * s.ncg * (plan->nperseg / 2 + 1) * sizeof(float4);
 }
 
@@ -252,16 +245,12 @@ int specenh_spectral_mean(const specenh_stft_plan* plan, const float* x, const f
                           long long y_stride, long long navg, float* pxx, float* pyy, void* pxy,
                           float* coh, void* workspace, void* stream) {
   using namespace specenh;
-  if (!plan) return set_error(SPECENH_EINVAL, "null plan");
   if (!x) return set_error(SPECENH_EINVAL, "null x");
-  if (batch < 0) return set_error(SPECENH_EINVAL, "batch must be >= 0");
-  if (x_stride < length || (y && y_stride < length))
-    return set_error(SPECENH_EINVAL, y && x_stride >= length ? "y_stride < length"
-                                                             : "x_stride < length");
-  const int N = plan->nperseg;
   FrameSplit s;
-  const int rc = frame_split(plan, length, navg, false, &s);
-  if (rc != SPECENH_OK) return rc;
+  if (int rc = check_call(plan, batch, length, navg, false, &s)) return rc;
+  const SignalArg in[] = {{x, x_stride, "x_stride < length"}, {y, y_stride, "y_stride < length"}};
+  if (int rc = check_strides(in, 2, length)) return rc;
+  const int N = plan->nperseg;
   if (!y && (pyy || pxy || coh))
     return set_error(SPECENH_EINVAL, "pyy, pxy and coh need a second signal y");
   if (!pxx && !pyy && !pxy && !coh) return set_error(SPECENH_EINVAL, "no output requested");
@@ -295,12 +284,8 @@ int specenh_spectral_mean(const specenh_stft_plan* plan, const float* x, const f
     a.o.pxy = pxy ? reinterpret_cast<float2*>(pxy) + o0 : nullptr;
     a.o.coh = coh ? coh + o0 : nullptr;
     a.ws = s.ncg > 1 ? (char*)workspace + (size_t)(b0 * s.G * s.ncg * F) * ws_elem : nullptr;
-    note_launch(reinterpret_cast<const void*>(kern));
-    hipLaunchKernelGGL(kern, dim3((unsigned)(s.G * s.ncg), (unsigned)nb), dim3(CT), lds,
-                       (hipStream_t)stream, a);
-    e = hipGetLastError();
-    if (e != hipSuccess)
-      return set_error(SPECENH_EHIP, std::string("spectral_mean launch: ") + hipGetErrorString(e));
+    launch(kern, dim3((unsigned)(s.G * s.ncg), (unsigned)nb), dim3(CT), lds, stream, a);
+    if (int rc = launched("spectral_mean")) return rc;
     if (s.ncg == 1) continue;
     FinArgs f{};
     f.ws = a.ws; f.total = nb * s.G * F; f.F = (int)F; f.G = (int)s.G; f.ncg = (int)s.ncg;
@@ -312,10 +297,7 @@ int specenh_spectral_mean(const specenh_stft_plan* plan, const float* x, const f
     else
       SPECENH_LAUNCH(spectral_finalize_kernel<false>, dim3((unsigned)blocks), dim3(CT), 0,
                      (hipStream_t)stream, f);
-    e = hipGetLastError();
-    if (e != hipSuccess)
-      return set_error(SPECENH_EHIP,
-                       std::string("spectral_finalize launch: ") + hipGetErrorString(e));
+    if (int rc = launched("spectral_finalize")) return rc;
   }
   return SPECENH_OK;
 }

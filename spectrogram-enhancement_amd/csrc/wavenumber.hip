@@ -3,7 +3,7 @@
 // the per-frame cross-phase theta = arg(conj(X_t[f]) Y_t[f]) over K centred bins, each frame
 // weighted by its power o[f] (|X_t[f]|^2 + |Y_t[f]|^2) / 2. Two kernels on one stream:
 //
-// the transform of bispectrum.hip (transform_frames(), stft_plan.hpp): every frame of x and y
+// the transform of bispectrum.hip (transform_frames(), averaging.hpp): every frame of x and y
 //   that enters a group, detrended, windowed and transformed once into the workspace as
 //   float2 [shot][signal][frame][F] holding 2 X / sqrt(scale);
 //
@@ -29,7 +29,7 @@
 
 #include "specenh_wavenumber.h"
 #include "runtime.hpp"
-#include "stft_plan.hpp"
+#include "averaging.hpp"
 
 namespace specenh {
 namespace {
@@ -145,10 +145,7 @@ int accumulate(AccumulateArgs g, long long batch, float* skf, void* stream) {
     g.S = skf + b0 * out_shot;
     SPECENH_LAUNCH(wavenumber_accumulate_kernel, dim3((unsigned)per_shot, (unsigned)nb), dim3(WL),
                    lds, (hipStream_t)stream, g);
-    e = hipGetLastError();
-    if (e != hipSuccess)
-      return set_error(SPECENH_EHIP,
-                       std::string("wavenumber_accumulate launch: ") + hipGetErrorString(e));
+    if (int rc = launched("wavenumber_accumulate")) return rc;
   }
   return SPECENH_OK;
 }
@@ -163,21 +160,12 @@ size_t specenh_wavenumber_workspace_bytes(const specenh_stft_plan* plan, long lo
                                           long long navg) {
   using namespace specenh;
   FrameSplit s;
-  if (!plan) {
-    set_error(SPECENH_EINVAL, "null plan");
-    return 0;
-  }
+  if (check_call(plan, batch, length, navg, true, &s) != SPECENH_OK) return 0;
   if (nsignals < 1 || nsignals > 2) {
     set_error(SPECENH_EINVAL, "nsignals must be in [1, 2]");
     return 0;
   }
-  if (batch < 0) {
-    set_error(SPECENH_EINVAL, "batch must be >= 0");
-    return 0;
-  }
-  if (frame_split(plan, length, navg, true, &s) != SPECENH_OK) return 0;
-  return (size_t)batch * (size_t)nsignals * (size_t)s.Tu * (size_t)(plan->nperseg / 2 + 1) * 2 *
-         sizeof(float);
+  return frames_workspace_bytes(plan, batch, nsignals, s.Tu);
 }
 
 int specenh_wavenumber_spectrum(const specenh_stft_plan* plan, const float* x, const float* y,
@@ -185,38 +173,27 @@ int specenh_wavenumber_spectrum(const specenh_stft_plan* plan, const float* x, c
                                 long long y_stride, long long navg, long long nk, float* skf,
                                 void* workspace, size_t workspace_bytes, void* stream) {
   using namespace specenh;
-  if (!plan) return set_error(SPECENH_EINVAL, "null plan");
   if (!x) return set_error(SPECENH_EINVAL, "null x");
   if (!y) return set_error(SPECENH_EINVAL, "null y");
-  if (batch < 0) return set_error(SPECENH_EINVAL, "batch must be >= 0");
   FrameSplit s;
-  int rc = frame_split(plan, length, navg, true, &s);
-  if (rc != SPECENH_OK) return rc;
-  if (x_stride < length) return set_error(SPECENH_EINVAL, "x_stride < length");
-  if (y_stride < length) return set_error(SPECENH_EINVAL, "y_stride < length");
-  if ((rc = check_nk(nk)) != SPECENH_OK) return rc;
+  if (int rc = check_call(plan, batch, length, navg, true, &s)) return rc;
+  const SignalArg in[] = {{x, x_stride, "x_stride < length"}, {y, y_stride, "y_stride < length"}};
+  if (int rc = check_strides(in, 2, length)) return rc;
+  if (int rc = check_nk(nk)) return rc;
   if (!skf) return set_error(SPECENH_EINVAL, "null skf");
   if (batch == 0) return SPECENH_OK;
   FrameSignals sig{};
-  sig.p[0] = x;
-  sig.stride[0] = x_stride;
-  int nsig = 1;
-  if (y != x || y_stride != x_stride) {
-    sig.p[1] = y;
-    sig.stride[1] = y_stride;
-    nsig = 2;
-  }
-  if (!workspace) return set_error(SPECENH_EINVAL, "null workspace");
-  if (reinterpret_cast<size_t>(workspace) % 16)
-    return set_error(SPECENH_EINVAL, "workspace must be 16-byte aligned");
-  if (workspace_bytes < specenh_wavenumber_workspace_bytes(plan, batch, nsig, length, navg))
-    return set_error(SPECENH_EINVAL, "workspace too small");
-  rc = transform_frames(plan, sig, nsig, batch, s.Tu, workspace, (hipStream_t)stream);
-  if (rc != SPECENH_OK) return rc;
+  int which[2];
+  const int nsig = collect_signals(in, 2, &sig, which);  // y given as x: transformed once
+  if (int rc = check_workspace(workspace, workspace_bytes,
+                               frames_workspace_bytes(plan, batch, nsig, s.Tu)))
+    return rc;
+  if (int rc = transform_frames(plan, sig, nsig, batch, s.Tu, workspace, (hipStream_t)stream))
+    return rc;
   const long long F = plan->nperseg / 2 + 1;
   AccumulateArgs g{};
   g.X = reinterpret_cast<const float2*>(workspace);
-  g.Y = g.X + (nsig - 1) * s.Tu * F;
+  g.Y = g.X + which[1] * s.Tu * F;
   g.bs = (long long)nsig * s.Tu * F;
   g.F = (int)F; g.K = (int)nk; g.G = (int)s.G; g.glen = (int)s.glen;
   g.nt = (int)((F + WL - 1) / WL);
@@ -231,13 +208,9 @@ int specenh_wavenumber_spectra(const void* X, const void* Y, long long batch, lo
   using namespace specenh;
   if (!X) return set_error(SPECENH_EINVAL, "null X");
   if (!Y) return set_error(SPECENH_EINVAL, "null Y");
-  if (batch < 0) return set_error(SPECENH_EINVAL, "batch must be >= 0");
-  if (nfreq < 1 || nfreq > 2049) return set_error(SPECENH_EINVAL, "nfreq must be in [1, 2049]");
-  if (frames > (1ll << 30)) return set_error(SPECENH_EINVAL, "too many frames");
-  const long long G = specenh_spectral_groups(frames, navg);
-  if (G < 0) return (int)G;
-  const int rc = check_nk(nk);
-  if (rc != SPECENH_OK) return rc;
+  long long G;
+  if (int rc = check_spectra(batch, frames, nfreq, navg, &G)) return rc;
+  if (int rc = check_nk(nk)) return rc;
   if (!skf) return set_error(SPECENH_EINVAL, "null skf");
   if (batch == 0) return SPECENH_OK;
   AccumulateArgs g{};

@@ -25,8 +25,9 @@ from __future__ import annotations
 import torch
 
 from . import _lib
-from .spectral import _prep, group_times
-from .stft import _check_nperseg, _norm_detrend, _norm_scaling, frequencies
+from .spectral import (_capped, _gpu_only, _groups, _plan_args, _prep, _same, _signals, _spectra,
+                       _spectra_groups, group_times)
+from .stft import frequencies
 
 _BITS = {"bispec": _lib.BISPEC_BISPEC, "bicoh": _lib.BISPEC_BICOH}
 _DTYPES = {"bispec": torch.complex64, "bicoh": torch.float32}
@@ -50,11 +51,6 @@ def _nbins(nbins, F):
     return K
 
 
-def _same(a, b):
-    return (a.data_ptr() == b.data_ptr() and a.shape == b.shape and a.stride() == b.stride()
-            and a.dtype == b.dtype)
-
-
 def bispectrum(x: torch.Tensor, y: torch.Tensor | None = None, z: torch.Tensor | None = None,
                fs: float = 1.0, window="hann", nperseg: int = 256, noverlap=None,
                detrend="constant", scaling="density", navg=None, nbins=None,
@@ -68,51 +64,28 @@ def bispectrum(x: torch.Tensor, y: torch.Tensor | None = None, z: torch.Tensor |
     consecutive frames, the leftover frames dropped. 1-D input drops ``B``.
     """
     from .ops import ops, bispectrum_workspace, window_key
-    nperseg, noverlap = _check_nperseg(nperseg, noverlap)
-    sc, dt = _norm_scaling(scaling), _norm_detrend(detrend)
-    for name, v in (("x", x), ("y", y), ("z", z)):
-        if v is not None and not isinstance(v, torch.Tensor):
-            raise TypeError(f"{name} must be a torch.Tensor")
-    if x.dim() not in (1, 2):
-        raise ValueError("x must be [batch, length]")
-    for v in (y, z):
-        if v is not None and (v.shape != x.shape or v.device != x.device):
-            raise ValueError("x, y and z must have the same shape and device")
-    squeeze = x.dim() == 1
+    nperseg, noverlap, sc, dt = _plan_args(nperseg, noverlap, scaling, detrend)
+    squeeze = _signals(x=x, y=y, z=z)
     want = _want(want)
-    F = nperseg // 2 + 1
-    K = _nbins(nbins, F)
+    K = _nbins(nbins, nperseg // 2 + 1)
     L = x.shape[-1]
-    if L < nperseg:
-        raise ValueError(f"signal of {L} samples is shorter than nperseg = {nperseg}")
-    navg = int(navg or 0)
-    T = (L - nperseg) // (nperseg - noverlap) + 1
-    if navg > T:
-        raise ValueError(f"navg = {navg} exceeds the number of frames ({T})")
-    if x.device.type != "cuda":
-        raise RuntimeError("specenh.bispectrum runs on the GPU only (no CPU fallback); "
-                           "move the signals to a ROCm device first")
+    navg, _, G = _groups(L, nperseg, noverlap, navg)
+    _gpu_only(x, "bispectrum")
     # a signal given twice is transformed once: the same tensor stays the same tensor
     xs = _prep(x)
     ys = xs if y is None or _same(y, x) else _prep(y)
     zs = xs if z is None or _same(z, x) else (ys if y is not None and _same(z, y) else _prep(z))
-    nsig = len({id(v) for v in (xs, ys, zs)})
     ys, zs = (None if ys is xs else ys), (None if zs is xs else zs)
     B = xs.shape[0]
-    G = 1 if navg <= 0 else T // navg
     args = (nperseg, noverlap, window_key(window, nperseg), float(fs), sc, dt, navg)
     outs = [torch.empty((B, G, K, K), dtype=_DTYPES[w], device=x.device) if w in want else None
             for w in _BITS]
-    per_shot = 8 * nsig * G * (navg if navg >= 1 else T) * F  # workspace bytes a shot
-    step = max(1, int(CSM_WORKSPACE_CAP) // per_shot)
-    sl = slice(0, min(step, B))
-    ws = bispectrum_workspace(xs[sl], None if ys is None else ys[sl],
-                              None if zs is None else zs[sl], *args) if B else None
-    for b0 in range(0, B, step):
-        sl = slice(b0, min(B, b0 + step))
-        ops.bispectrum_out(xs[sl], None if ys is None else ys[sl],
-                           None if zs is None else zs[sl], *args, K,
-                           *(None if o is None else o[sl] for o in outs), ws)
+
+    def one_shot():
+        return bispectrum_workspace(*(None if v is None else v[:1] for v in (xs, ys, zs)), *args)
+
+    for cut, ws in _capped(B, CSM_WORKSPACE_CAP, one_shot):
+        ops.bispectrum_out(cut(xs), cut(ys), cut(zs), *args, K, cut(outs[0]), cut(outs[1]), ws)
     est = {w: (o[0] if squeeze else o) for w, o in zip(_BITS, outs) if o is not None}
     return frequencies(nperseg, fs)[:K], group_times(L, nperseg, noverlap, fs, navg), est
 
@@ -135,33 +108,11 @@ def bispectrum_from_spectra(X: torch.Tensor, Y: torch.Tensor | None = None,
     ``k + l <= F - 1``). No scaling is applied. Returns ``est`` as ``bispectrum`` does,
     ``[B, G, K, K]``; ``X[T, F]`` drops ``B``."""
     from .ops import ops
-    for name, v in (("X", X), ("Y", Y), ("Z", Z)):
-        if v is not None and not isinstance(v, torch.Tensor):
-            raise TypeError(f"{name} must be a torch.Tensor")
-    if not X.is_complex() or X.dim() not in (2, 3):
-        raise ValueError("X must be complex [batch, frames, F]")
-    for v in (Y, Z):
-        if v is not None and (v.shape != X.shape or v.device != X.device or not v.is_complex()):
-            raise ValueError("X, Y and Z must be complex and have the same shape and device")
-    squeeze = X.dim() == 2
+    squeeze, T, F, prep = _spectra(X=X, Y=Y, Z=Z)
     want = _want(want)
-    T, F = X.shape[-2], X.shape[-1]
-    if not 1 <= F <= 2049:
-        raise ValueError(f"F must be in [1, 2049], got {F}")
     K = _nbins(nbins, F)
-    navg = int(navg or 0)
-    if T < 1:
-        raise ValueError("the spectra must hold at least one frame")
-    if navg > T:
-        raise ValueError(f"navg = {navg} exceeds the number of frames ({T})")
-    if X.device.type != "cuda":
-        raise RuntimeError("specenh.bispectrum runs on the GPU only (no CPU fallback); "
-                           "move the spectra to a ROCm device first")
-
-    def prep(v):
-        v = v.unsqueeze(0) if squeeze else v
-        return v.to(torch.complex64).contiguous()
-
+    navg = _spectra_groups(T, navg)
+    _gpu_only(X, "bispectrum", "spectra")
     Xs = prep(X)
     Ys = None if Y is None or _same(Y, X) else prep(Y)
     Zs = None if Z is None or _same(Z, X) else prep(Z)

@@ -35,9 +35,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from .bispectrum import _same
-from .spectral import _prep, group_times
-from .stft import _check_nperseg, _norm_detrend, get_window
+from .spectral import (_capped, _gpu_only, _groups, _plan_args, _prep, _same, _signals,
+                       group_times)
+from .stft import get_window
 
 # One launch's workspace (a record per chunk of 32 frames when a group is longer than a chunk)
 # stays under this many bytes: the batch is split into several launches, a single shot above it
@@ -92,54 +92,33 @@ def correlate(x: torch.Tensor, y: torch.Tensor, window="boxcar", nperseg: int = 
     lag at which the product is 0 (the ends of a window that starts at 0) is then Inf or NaN.
     """
     from .ops import ops, correlation_workspace, window_key
-    nperseg, noverlap = _check_nperseg(nperseg, noverlap)
+    nperseg, noverlap, _, dt = _plan_args(nperseg, noverlap, "density", detrend)
     if nperseg > _lib.CORR_MAX_NPERSEG:
         raise NotImplementedError(
             f"correlate: nperseg = {nperseg} is not supported (the padded transform would be "
             f"{2 * nperseg} points); nperseg must be a power of two in [64, 2048]")
-    dt = _norm_detrend(detrend)
     try:
         mode = _MODES[normalize]
     except (KeyError, TypeError):
         raise ValueError(f"normalize must be 'coeff' or 'raw', got {normalize!r}") from None
-    for name, v in (("x", x), ("y", y)):
-        if not isinstance(v, torch.Tensor):
-            raise TypeError(f"{name} must be a torch.Tensor")
-    if x.dim() not in (1, 2):
-        raise ValueError("x must be [batch, length]")
-    if y.shape != x.shape or y.device != x.device:
-        raise ValueError("x and y must have the same shape and device")
-    squeeze = x.dim() == 1
+    squeeze = _signals(True, x=x, y=y)
     M = _maxlag(maxlag, nperseg)
     L = x.shape[-1]
-    if L < nperseg:
-        raise ValueError(f"signal of {L} samples is shorter than nperseg = {nperseg}")
-    navg = int(navg or 0)
-    T = (L - nperseg) // (nperseg - noverlap) + 1
-    if navg > T:
-        raise ValueError(f"navg = {navg} exceeds the number of frames ({T})")
+    navg, _, G = _groups(L, nperseg, noverlap, navg)
     div = None
     if unbiased:
         c = window_lag_product(window, nperseg, M)
         div = c / c[M] if mode == _lib.CORR_COEFF else c
-    if x.device.type != "cuda":
-        raise RuntimeError("specenh.correlation runs on the GPU only (no CPU fallback); "
-                           "move the signals to a ROCm device first")
+    _gpu_only(x, "correlation")
     xs = _prep(x)
     ys = xs if _same(y, x) else _prep(y)  # a signal given twice is loaded and transformed once
     B = xs.shape[0]
-    glen = navg if navg >= 1 else T
-    G = T // glen
-    ncg = -(-glen // _lib.SPECTRAL_CHUNK)
     args = (nperseg, noverlap, window_key(window, nperseg), float(fs), 0, dt, navg, M)
     R = torch.empty((B, G, 2 * M + 1), dtype=torch.float32, device=x.device)
-    per_shot = 8 * (nperseg + 3) * G * ncg if ncg > 1 else 0  # workspace bytes a shot
-    step = max(1, int(CSM_WORKSPACE_CAP) // per_shot) if per_shot else max(B, 1)
-    sl = slice(0, min(step, B))
-    ws = correlation_workspace(xs[sl], ys[sl], *args) if B else None
-    for b0 in range(0, B, step):
-        sl = slice(b0, min(B, b0 + step))
-        ops.correlation_out(xs[sl], ys[sl], *args, mode, R[sl], None, ws)
+    # a group of one chunk needs no workspace: then the batch is one launch
+    for cut, ws in _capped(B, CSM_WORKSPACE_CAP,
+                           lambda: correlation_workspace(xs[:1], ys[:1], *args)):
+        ops.correlation_out(cut(xs), cut(ys), *args, mode, cut(R), None, ws)
     if div is not None:
         R = (R.double() / torch.as_tensor(div, device=R.device)).float()
     return (correlation_lags(M, fs), group_times(L, nperseg, noverlap, fs, navg),

@@ -258,96 +258,193 @@ _op("csd(Tensor x, Tensor y, int nperseg, int noverlap, str window, float fs, in
     "int detrend, int mode) -> Tensor", _csd, _csd_fake)
 
 
+# ---------------------------------------------------------------- averaging operators
+# What spectral_mean, csm, bispectrum, wavenumber_spectrum and correlation share. `sig` is
+# ((name, tensor or None), ...), its first signal present; `p` is the plan's arguments
+# (nperseg, noverlap, window, fs, scaling, detrend). An operator's `_call` runs the checks
+# once, takes the caller's outputs or allocates them from the `outputs` mask, and launches.
+_F32 = (torch.float32,)
+
+
+def _avg_split(length, nperseg, noverlap, navg):
+    """(frames, groups) of a call; plain arithmetic, on symbolic sizes too."""
+    T = (length - nperseg) // (nperseg - noverlap) + 1
+    return T, (1 if navg <= 0 else T // navg)
+
+
+def _avg_check_split(length, nperseg, noverlap, navg):
+    if noverlap >= nperseg:
+        raise ValueError("noverlap must be less than nperseg.")
+    if length < nperseg:
+        raise ValueError("signal shorter than nperseg")
+    T, G = _avg_split(length, nperseg, noverlap, navg)
+    if navg > T:
+        raise ValueError(f"navg = {navg} exceeds the number of frames ({T})")
+    return T, G
+
+
+def _avg_names(sig):
+    names = [name for name, _ in sig]
+    return ", ".join(names[:-1]) + " and " + names[-1]
+
+
+def _avg_check(sig, nperseg, noverlap, navg):
+    """Signals [batch, length], each like the first; (frames, groups) of the call."""
+    x = sig[0][1]
+    shape, device = x.shape, x.device
+    for name, v in sig:
+        if v is None:
+            continue
+        if v.dim() != 2 or v.stride(1) != 1 or v.dtype != torch.float32:
+            raise ValueError(f"{name} must be float32 [batch, length] with unit stride along "
+                             "length")
+        if v is not x and (v.shape != shape or v.device != device):
+            raise ValueError(f"{_avg_names(sig)} must have the same shape and device")
+    return _avg_check_split(shape[1], nperseg, noverlap, navg)
+
+
+def _avg_spectra(sig, navg):
+    """Spectra [batch, frames, F], each like the first; (B, T, F, groups)."""
+    X = sig[0][1]
+    for name, v in sig:
+        if v is None:
+            continue
+        if v.dim() != 3 or v.dtype != torch.complex64 or not v.is_contiguous():
+            raise ValueError(f"{name} must be contiguous complex64 [batch, frames, F]")
+        if v.shape != X.shape or v.device != X.device:
+            raise ValueError(f"{_avg_names(sig)} must have the same shape and device")
+    B, T, F = X.shape
+    if not 1 <= F <= 2049:
+        raise ValueError(f"F must be in [1, 2049], got {F}")
+    if T < 1:
+        raise ValueError("the spectra must hold at least one frame")
+    if navg > T:
+        raise ValueError(f"navg = {navg} exceeds the number of frames ({T})")
+    return B, T, F, (1 if navg <= 0 else T // navg)
+
+
+def _avg_stride(v):
+    """Batch stride of v[B, L], 0 for an absent signal; the stride of a one-element axis is
+    free."""
+    if v is None:
+        return 0
+    B, L = v.shape
+    s = v.stride(0) if B > 1 else L
+    if s < L:
+        raise ValueError("a signal must not overlap itself: batch stride >= length")
+    return s
+
+
+def _avg_distinct(signals, strides):
+    """How many of the signals are distinct in pointer and stride, as the C entries count."""
+    return len({(v.data_ptr(), s) for v, s in zip(signals, strides) if v is not None})
+
+
+def _avg_plan(x, p, symbol, *extra, may_be_zero=False):
+    """The plan of a call and the bytes its workspace needs: specenh_<symbol>(plan, *extra),
+    extra[0] the batch. 0 is an error unless the operator can do without a workspace."""
+    from . import stft
+    plan = stft.get_plan_key(x.device, *p, 0.0)
+    need = int(getattr(_lib.lib(), "specenh_" + symbol)(plan.handle, *extra))
+    if need == 0 and extra[0] > 0 and not may_be_zero:
+        _lib.check(_lib.SPECENH_EINVAL, symbol)
+    return plan, need
+
+
+def _avg_buffer(need, device):
+    return torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+
+
+def _avg_workspace(workspace, need, device):
+    """(workspace, its bytes) for a call that needs `need` bytes: the caller's, checked, or a new
+    one; (None, 0) when none is needed."""
+    if need == 0:
+        return None, 0
+    if workspace is None:
+        workspace = _avg_buffer(need, device)
+    nbytes = workspace.numel() * workspace.element_size()
+    if (workspace.device != device or not workspace.is_contiguous() or nbytes < need
+            or workspace.data_ptr() % 16):
+        raise ValueError(f"workspace must be a contiguous, 16-byte aligned buffer of at least "
+                         f"{need} bytes on x's device")
+    return workspace, nbytes
+
+
+def _avg_outs(x, outs, mask, shape, dtypes, what):
+    """The outputs of a call, one per dtype or None: the caller's `outs`, checked, or (outs
+    None) allocated where bit i of `mask` is set."""
+    if outs is None:
+        outs = [torch.empty(shape, dtype=dt, device=x.device) if mask >> i & 1 else None
+                for i, dt in enumerate(dtypes)]
+    none, device = True, x.device
+    for o, dt in zip(outs, dtypes):
+        if o is None:
+            continue
+        none = False
+        if o.shape != shape or o.dtype != dt or not o.is_contiguous() or o.device != device:
+            raise ValueError(f"outputs must be contiguous {shape} on x's device ({what})")
+    if none:
+        raise ValueError("no output requested")
+    return outs
+
+
+def _avg_results(x, outs, dtypes):
+    """What an allocating operator returns: an empty placeholder for an output not asked for."""
+    return tuple(x.new_empty((0,), dtype=dt) if o is None else o for o, dt in zip(outs, dtypes))
+
+
+def _avg_fake(x, mask, shape, dtypes):
+    return tuple(x.new_empty(shape if mask >> i & 1 else (0,), dtype=dt)
+                 for i, dt in enumerate(dtypes))
+
+
+_SP_ARGS = "int nperseg, int noverlap, str window, float fs, int scaling, int detrend, int navg"
+
 # ---------------------------------------------------------------- averaged spectra
 _SP_DTYPES = (torch.float32, torch.float32, torch.complex64, torch.float32)
 
 
-def _sp_groups(T, navg):
-    return 1 if navg <= 0 else T // navg
-
-
-def _sp_shape(x, nperseg, noverlap, navg):
-    T = (x.shape[1] - nperseg) // (nperseg - noverlap) + 1
-    return x.shape[0], nperseg // 2 + 1, _sp_groups(T, navg)
+def _spectral_mean_call(x, y, p, navg, outs, mask, workspace):
+    _, G = _avg_check((("x", x), ("y", y)), p[0], p[1], navg)
+    B, L = x.shape
+    outs = _avg_outs(x, outs, mask, (B, p[0] // 2 + 1, G), _SP_DTYPES,
+                     "pxx, pyy, coh float32, pxy complex64")
+    if y is None and any(o is not None for o in outs[1:]):
+        raise ValueError("pyy, pxy and coh need a second signal y")
+    plan, need = _avg_plan(x, p, "spectral_workspace_bytes", B, L, int(navg), may_be_zero=True)
+    ws, _ = _avg_workspace(workspace, need, x.device)
+    _lib.check(_lib.lib().specenh_spectral_mean(
+        plan.handle, _vp(x), _vp(y), B, L, _avg_stride(x), _avg_stride(y), int(navg),
+        _vp(outs[0]), _vp(outs[1]), _vp(outs[2]), _vp(outs[3]), _vp(ws), _st(x)), "spectral_mean")
+    return outs
 
 
 def _spectral_mean_out(x, y, nperseg, noverlap, window, fs, scaling, detrend, navg, pxx, pyy, pxy,
                        coh, workspace):
-    from . import stft
-    for name, v in (("x", x), ("y", y)):
-        if v is not None and (v.dim() != 2 or v.stride(1) != 1 or v.dtype != torch.float32):
-            raise ValueError(f"{name} must be float32 [batch, length] with unit stride along "
-                             "length")
-    if y is not None and (y.shape != x.shape or y.device != x.device):
-        raise ValueError("x and y must have the same shape and device")
-    if noverlap >= nperseg:
-        raise ValueError("noverlap must be less than nperseg.")
-    B, L = x.shape
-    if L < nperseg:
-        raise ValueError("signal shorter than nperseg")
-    T = (L - nperseg) // (nperseg - noverlap) + 1
-    if navg > T:
-        raise ValueError(f"navg = {navg} exceeds the number of frames ({T})")
-    outs = (pxx, pyy, pxy, coh)
-    if all(o is None for o in outs):
-        raise ValueError("no output requested")
-    if y is None and any(o is not None for o in outs[1:]):
-        raise ValueError("pyy, pxy and coh need a second signal y")
-    shape = _sp_shape(x, nperseg, noverlap, navg)
-    for o, dt in zip(outs, _SP_DTYPES):
-        if o is not None and (tuple(o.shape) != shape or o.dtype != dt or not o.is_contiguous()
-                              or o.device != x.device):
-            raise ValueError(f"outputs must be contiguous {shape} on x's device (pxx, pyy, coh "
-                             "float32, pxy complex64)")
-    plan = stft.get_plan_key(x.device, nperseg, noverlap, window, fs, scaling, detrend, 0.0)
-    L_ = _lib.lib()
-    need = int(L_.specenh_spectral_workspace_bytes(plan.handle, B, L, navg))
-    if need and (workspace is None or workspace.device != x.device
-                 or not workspace.is_contiguous()
-                 or workspace.numel() * workspace.element_size() < need
-                 or workspace.data_ptr() % 16):
-        raise ValueError(f"workspace must be a contiguous, 16-byte aligned buffer of at least "
-                         f"{need} bytes on x's device")
-    _lib.check(L_.specenh_spectral_mean(
-        plan.handle, _vp(x), _vp(y), B, L, x.stride(0) if B > 1 else L,
-        (y.stride(0) if B > 1 else L) if y is not None else 0, int(navg), _vp(pxx), _vp(pyy),
-        _vp(pxy), _vp(coh), _vp(workspace if need else None), _st(x)), "spectral_mean")
+    _spectral_mean_call(x, y, (nperseg, noverlap, window, fs, scaling, detrend), navg,
+                        (pxx, pyy, pxy, coh), 0, workspace)
 
 
 def spectral_workspace(x, nperseg, noverlap, window, fs, scaling, detrend, navg):
     """A workspace for ``spectral_mean_out`` on ``x[B, L]`` (uint8; one byte when none is
     needed), from torch's caching allocator."""
-    from . import stft
-    plan = stft.get_plan_key(x.device, nperseg, noverlap, window, fs, scaling, detrend, 0.0)
-    need = int(_lib.lib().specenh_spectral_workspace_bytes(plan.handle, x.shape[0], x.shape[1],
-                                                           int(navg)))
-    return torch.empty(max(need, 1), dtype=torch.uint8, device=x.device)
+    _, need = _avg_plan(x, (nperseg, noverlap, window, fs, scaling, detrend),
+                        "spectral_workspace_bytes", x.shape[0], x.shape[1], int(navg),
+                        may_be_zero=True)
+    return _avg_buffer(need, x.device)
 
 
 def _spectral_mean(x, y, nperseg, noverlap, window, fs, scaling, detrend, navg, outputs):
-    if noverlap >= nperseg:
-        raise ValueError("noverlap must be less than nperseg.")
-    if x.dim() != 2 or x.dtype != torch.float32 or x.shape[1] < nperseg:
-        raise ValueError("x must be float32 [batch, length] with length >= nperseg")
-    T = (x.shape[1] - nperseg) // (nperseg - noverlap) + 1
-    if navg > T:
-        raise ValueError(f"navg = {navg} exceeds the number of frames ({T})")
-    shape = _sp_shape(x, nperseg, noverlap, navg)
-    outs = [torch.empty(shape, dtype=dt, device=x.device) if outputs >> i & 1 else None
-            for i, dt in enumerate(_SP_DTYPES)]
-    ws = spectral_workspace(x, nperseg, noverlap, window, fs, scaling, detrend, navg)
-    _spectral_mean_out(x, y, nperseg, noverlap, window, fs, scaling, detrend, navg, *outs, ws)
-    return tuple(x.new_empty((0,), dtype=dt) if o is None else o
-                 for o, dt in zip(outs, _SP_DTYPES))
+    return _avg_results(x, _spectral_mean_call(
+        x, y, (nperseg, noverlap, window, fs, scaling, detrend), navg, None, outputs, None),
+        _SP_DTYPES)
 
 
 def _spectral_mean_fake(x, y, nperseg, noverlap, window, fs, scaling, detrend, navg, outputs):
-    shape = _sp_shape(x, nperseg, noverlap, navg)
-    return tuple(x.new_empty(shape if outputs >> i & 1 else (0,), dtype=dt)
-                 for i, dt in enumerate(_SP_DTYPES))
+    G = _avg_split(x.shape[1], nperseg, noverlap, navg)[1]
+    return _avg_fake(x, outputs, (x.shape[0], nperseg // 2 + 1, G), _SP_DTYPES)
 
 
-_SP_ARGS = "int nperseg, int noverlap, str window, float fs, int scaling, int detrend, int navg"
 _op(f"spectral_mean(Tensor x, Tensor? y, {_SP_ARGS}, int outputs) -> "
     "(Tensor, Tensor, Tensor, Tensor)", _spectral_mean, _spectral_mean_fake)
 _op(f"spectral_mean_out(Tensor x, Tensor? y, {_SP_ARGS}, Tensor(a!)? pxx, Tensor(b!)? pyy, "
@@ -359,26 +456,13 @@ _op(f"spectral_mean_out(Tensor x, Tensor? y, {_SP_ARGS}, Tensor(a!)? pxx, Tensor
 _CSM_DTYPES = (torch.complex64, torch.float32)
 
 
-def _csm_shape(x, nperseg, noverlap, navg):
-    T = (x.shape[2] - nperseg) // (nperseg - noverlap) + 1
-    C = x.shape[1]
-    return x.shape[0], nperseg // 2 + 1, _sp_groups(T, navg), C, C
-
-
 def _csm_check(x, nperseg, noverlap, navg):
     if x.dim() != 3 or x.dtype != torch.float32 or x.stride(2) != 1:
         raise ValueError("x must be float32 [batch, channels, length] with unit stride along "
                          "length")
-    if noverlap >= nperseg:
-        raise ValueError("noverlap must be less than nperseg.")
-    B, C, L = x.shape
-    if not 2 <= C <= _lib.CSM_MAX_CHANNELS:
-        raise ValueError(f"channels must be in [2, {_lib.CSM_MAX_CHANNELS}], got {C}")
-    if L < nperseg:
-        raise ValueError("signal shorter than nperseg")
-    T = (L - nperseg) // (nperseg - noverlap) + 1
-    if navg > T:
-        raise ValueError(f"navg = {navg} exceeds the number of frames ({T})")
+    if not 2 <= x.shape[1] <= _lib.CSM_MAX_CHANNELS:
+        raise ValueError(f"channels must be in [2, {_lib.CSM_MAX_CHANNELS}], got {x.shape[1]}")
+    return _avg_check_split(x.shape[2], nperseg, noverlap, navg)
 
 
 def _csm_strides(x):
@@ -392,65 +476,42 @@ def _csm_strides(x):
     return cs, bs
 
 
-def _csm_need(x, nperseg, noverlap, window, fs, scaling, detrend, navg):
-    from . import stft
-    plan = stft.get_plan_key(x.device, nperseg, noverlap, window, fs, scaling, detrend, 0.0)
-    B, C, L = x.shape
-    need = int(_lib.lib().specenh_csm_workspace_bytes(plan.handle, B, C, L, int(navg)))
-    if need == 0 and B > 0:
-        _lib.check(_lib.SPECENH_EINVAL, "csm_workspace_bytes")
-    return plan, need
-
-
 def csm_workspace(x, nperseg, noverlap, window, fs, scaling, detrend, navg):
     """A workspace for ``csm_out`` on ``x[B, C, L]`` (uint8, from torch's caching allocator):
     the spectra of every frame that enters a group, ``8 B F T C`` bytes."""
     _csm_check(x, nperseg, noverlap, navg)
-    _, need = _csm_need(x, nperseg, noverlap, window, fs, scaling, detrend, navg)
-    return torch.empty(max(need, 1), dtype=torch.uint8, device=x.device)
+    _, need = _avg_plan(x, (nperseg, noverlap, window, fs, scaling, detrend),
+                        "csm_workspace_bytes", *x.shape, int(navg))
+    return _avg_buffer(need, x.device)
+
+
+def _csm_call(x, p, navg, outs, mask, workspace):
+    _, G = _csm_check(x, p[0], p[1], navg)
+    cs, bs = _csm_strides(x)
+    B, C, L = x.shape
+    outs = _avg_outs(x, outs, mask, (B, p[0] // 2 + 1, G, C, C), _CSM_DTYPES,
+                     "csm complex64, coh float32")
+    plan, need = _avg_plan(x, p, "csm_workspace_bytes", B, C, L, int(navg))
+    ws, nbytes = _avg_workspace(workspace, need, x.device)
+    _lib.check(_lib.lib().specenh_csm(
+        plan.handle, _vp(x), B, C, L, cs, bs, int(navg), _vp(outs[0]), _vp(outs[1]), _vp(ws),
+        nbytes, _st(x)), "csm")
+    return outs
 
 
 def _csm_out(x, nperseg, noverlap, window, fs, scaling, detrend, navg, csm, coh, workspace):
-    _csm_check(x, nperseg, noverlap, navg)
-    cs, bs = _csm_strides(x)
-    outs = (csm, coh)
-    if all(o is None for o in outs):
-        raise ValueError("no output requested")
-    shape = _csm_shape(x, nperseg, noverlap, navg)
-    for o, dt in zip(outs, _CSM_DTYPES):
-        if o is not None and (tuple(o.shape) != shape or o.dtype != dt or not o.is_contiguous()
-                              or o.device != x.device):
-            raise ValueError(f"outputs must be contiguous {shape} on x's device (csm complex64, "
-                             "coh float32)")
-    plan, need = _csm_need(x, nperseg, noverlap, window, fs, scaling, detrend, navg)
-    if workspace is None:
-        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=x.device)
-    if (workspace.device != x.device or not workspace.is_contiguous()
-            or workspace.numel() * workspace.element_size() < need or workspace.data_ptr() % 16):
-        raise ValueError(f"workspace must be a contiguous, 16-byte aligned buffer of at least "
-                         f"{need} bytes on x's device")
-    B, C, L = x.shape
-    _lib.check(_lib.lib().specenh_csm(
-        plan.handle, _vp(x), B, C, L, cs, bs, int(navg), _vp(csm), _vp(coh), _vp(workspace),
-        workspace.numel() * workspace.element_size(), _st(x)), "csm")
+    _csm_call(x, (nperseg, noverlap, window, fs, scaling, detrend), navg, (csm, coh), 0, workspace)
 
 
 def _csm(x, nperseg, noverlap, window, fs, scaling, detrend, navg, outputs):
-    _csm_check(x, nperseg, noverlap, navg)
-    if not outputs & 3:
-        raise ValueError("no output requested")
-    shape = _csm_shape(x, nperseg, noverlap, navg)
-    outs = [torch.empty(shape, dtype=dt, device=x.device) if outputs >> i & 1 else None
-            for i, dt in enumerate(_CSM_DTYPES)]
-    _csm_out(x, nperseg, noverlap, window, fs, scaling, detrend, navg, *outs, None)
-    return tuple(x.new_empty((0,), dtype=dt) if o is None else o
-                 for o, dt in zip(outs, _CSM_DTYPES))
+    return _avg_results(x, _csm_call(x, (nperseg, noverlap, window, fs, scaling, detrend), navg,
+                                     None, outputs, None), _CSM_DTYPES)
 
 
 def _csm_fake(x, nperseg, noverlap, window, fs, scaling, detrend, navg, outputs):
-    shape = _csm_shape(x, nperseg, noverlap, navg)
-    return tuple(x.new_empty(shape if outputs >> i & 1 else (0,), dtype=dt)
-                 for i, dt in enumerate(_CSM_DTYPES))
+    B, C, L = x.shape
+    G = _avg_split(L, nperseg, noverlap, navg)[1]
+    return _avg_fake(x, outputs, (B, nperseg // 2 + 1, G, C, C), _CSM_DTYPES)
 
 
 _op(f"csm(Tensor x, {_SP_ARGS}, int outputs) -> (Tensor, Tensor)", _csm, _csm_fake)
@@ -460,6 +521,7 @@ _op(f"csm_out(Tensor x, {_SP_ARGS}, Tensor(a!)? csm, Tensor(b!)? coh, Tensor(c!)
 
 # ---------------------------------------------------------------- bispectrum, bicoherence
 _BISPEC_DTYPES = (torch.complex64, torch.float32)
+_BISPEC_OUTS = "bispec complex64, bicoh float32"
 
 
 def _bispec_bins(F, nbins):
@@ -469,165 +531,77 @@ def _bispec_bins(F, nbins):
     return K
 
 
-def _bispec_shape(x, nperseg, noverlap, navg, nbins):
-    T = (x.shape[1] - nperseg) // (nperseg - noverlap) + 1
-    K = _bispec_bins(nperseg // 2 + 1, nbins)
-    return x.shape[0], _sp_groups(T, navg), K, K
-
-
-def _bispec_check(x, y, z, nperseg, noverlap, navg):
-    for name, v in (("x", x), ("y", y), ("z", z)):
-        if v is not None and (v.dim() != 2 or v.stride(1) != 1 or v.dtype != torch.float32):
-            raise ValueError(f"{name} must be float32 [batch, length] with unit stride along "
-                             "length")
-        if v is not None and (v.shape != x.shape or v.device != x.device):
-            raise ValueError("x, y and z must have the same shape and device")
-    if noverlap >= nperseg:
-        raise ValueError("noverlap must be less than nperseg.")
-    B, L = x.shape
-    if L < nperseg:
-        raise ValueError("signal shorter than nperseg")
-    T = (L - nperseg) // (nperseg - noverlap) + 1
-    if navg > T:
-        raise ValueError(f"navg = {navg} exceeds the number of frames ({T})")
-
-
-def _bispec_stride(v):
-    """Batch stride of v[B, L]; the stride of a one-element axis is free."""
-    s = v.stride(0) if v.shape[0] > 1 else v.shape[1]
-    if s < v.shape[1]:
-        raise ValueError("a signal must not overlap itself: batch stride >= length")
-    return s
-
-
-def _bispec_distinct(x, y, z):
-    """Number of distinct signals among x, y, z, as specenh_bispectrum counts them."""
-    seen = [(x.data_ptr(), _bispec_stride(x))]
-    for v in (y, z):
-        if v is not None and (v.data_ptr(), _bispec_stride(v)) not in seen:
-            seen.append((v.data_ptr(), _bispec_stride(v)))
-    return len(seen)
-
-
-def _bispec_need(x, nsig, nperseg, noverlap, window, fs, scaling, detrend, navg):
-    from . import stft
-    plan = stft.get_plan_key(x.device, nperseg, noverlap, window, fs, scaling, detrend, 0.0)
-    B, L = x.shape
-    need = int(_lib.lib().specenh_bispectrum_workspace_bytes(plan.handle, B, nsig, L, int(navg)))
-    if need == 0 and B > 0:
-        _lib.check(_lib.SPECENH_EINVAL, "bispectrum_workspace_bytes")
-    return plan, need
-
-
 def bispectrum_workspace(x, y, z, nperseg, noverlap, window, fs, scaling, detrend, navg):
     """A workspace for ``bispectrum_out`` on ``x[B, L]`` (and ``y``, ``z``; uint8, from torch's
     caching allocator): the spectra of every frame that enters a group of every distinct
     signal, ``8 B nsignals T F`` bytes."""
-    _bispec_check(x, y, z, nperseg, noverlap, navg)
-    _, need = _bispec_need(x, _bispec_distinct(x, y, z), nperseg, noverlap, window, fs, scaling,
-                           detrend, navg)
-    return torch.empty(max(need, 1), dtype=torch.uint8, device=x.device)
+    _avg_check((("x", x), ("y", y), ("z", z)), nperseg, noverlap, navg)
+    _, need = _avg_plan(x, (nperseg, noverlap, window, fs, scaling, detrend),
+                        "bispectrum_workspace_bytes", x.shape[0],
+                        _avg_distinct((x, y, z), [_avg_stride(v) for v in (x, y, z)]), x.shape[1],
+                        int(navg))
+    return _avg_buffer(need, x.device)
 
 
-def _bispec_outputs(outs, shape, device):
-    if all(o is None for o in outs):
-        raise ValueError("no output requested")
-    for o, dt in zip(outs, _BISPEC_DTYPES):
-        if o is not None and (tuple(o.shape) != shape or o.dtype != dt or not o.is_contiguous()
-                              or o.device != device):
-            raise ValueError(f"outputs must be contiguous {shape} on x's device (bispec "
-                             "complex64, bicoh float32)")
+def _bispectrum_call(x, y, z, p, navg, nbins, outs, mask, workspace):
+    _, G = _avg_check((("x", x), ("y", y), ("z", z)), p[0], p[1], navg)
+    B, L = x.shape
+    K = _bispec_bins(p[0] // 2 + 1, nbins)
+    outs = _avg_outs(x, outs, mask, (B, G, K, K), _BISPEC_DTYPES, _BISPEC_OUTS)
+    strides = [_avg_stride(v) for v in (x, y, z)]
+    plan, need = _avg_plan(x, p, "bispectrum_workspace_bytes", B,
+                           _avg_distinct((x, y, z), strides), L, int(navg))
+    ws, nbytes = _avg_workspace(workspace, need, x.device)
+    _lib.check(_lib.lib().specenh_bispectrum(
+        plan.handle, _vp(x), _vp(y), _vp(z), B, L, *strides, int(navg), K, _vp(outs[0]),
+        _vp(outs[1]), _vp(ws), nbytes, _st(x)), "bispectrum")
+    return outs
 
 
 def _bispectrum_out(x, y, z, nperseg, noverlap, window, fs, scaling, detrend, navg, nbins, bispec,
                     bicoh, workspace):
-    _bispec_check(x, y, z, nperseg, noverlap, navg)
-    shape = _bispec_shape(x, nperseg, noverlap, navg, nbins)
-    _bispec_outputs((bispec, bicoh), shape, x.device)
-    nsig = _bispec_distinct(x, y, z)
-    plan, need = _bispec_need(x, nsig, nperseg, noverlap, window, fs, scaling, detrend, navg)
-    if workspace is None:
-        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=x.device)
-    if (workspace.device != x.device or not workspace.is_contiguous()
-            or workspace.numel() * workspace.element_size() < need or workspace.data_ptr() % 16):
-        raise ValueError(f"workspace must be a contiguous, 16-byte aligned buffer of at least "
-                         f"{need} bytes on x's device")
-    B, L = x.shape
-    _lib.check(_lib.lib().specenh_bispectrum(
-        plan.handle, _vp(x), _vp(y), _vp(z), B, L, _bispec_stride(x),
-        0 if y is None else _bispec_stride(y), 0 if z is None else _bispec_stride(z), int(navg),
-        shape[2], _vp(bispec), _vp(bicoh), _vp(workspace),
-        workspace.numel() * workspace.element_size(), _st(x)), "bispectrum")
+    _bispectrum_call(x, y, z, (nperseg, noverlap, window, fs, scaling, detrend), navg, nbins,
+                     (bispec, bicoh), 0, workspace)
 
 
 def _bispectrum(x, y, z, nperseg, noverlap, window, fs, scaling, detrend, navg, nbins, outputs):
-    _bispec_check(x, y, z, nperseg, noverlap, navg)
-    if not outputs & 3:
-        raise ValueError("no output requested")
-    shape = _bispec_shape(x, nperseg, noverlap, navg, nbins)
-    outs = [torch.empty(shape, dtype=dt, device=x.device) if outputs >> i & 1 else None
-            for i, dt in enumerate(_BISPEC_DTYPES)]
-    _bispectrum_out(x, y, z, nperseg, noverlap, window, fs, scaling, detrend, navg, nbins, *outs,
-                    None)
-    return tuple(x.new_empty((0,), dtype=dt) if o is None else o
-                 for o, dt in zip(outs, _BISPEC_DTYPES))
+    return _avg_results(x, _bispectrum_call(
+        x, y, z, (nperseg, noverlap, window, fs, scaling, detrend), navg, nbins, None, outputs,
+        None), _BISPEC_DTYPES)
 
 
 def _bispectrum_fake(x, y, z, nperseg, noverlap, window, fs, scaling, detrend, navg, nbins,
                      outputs):
-    shape = _bispec_shape(x, nperseg, noverlap, navg, nbins)
-    return tuple(x.new_empty(shape if outputs >> i & 1 else (0,), dtype=dt)
-                 for i, dt in enumerate(_BISPEC_DTYPES))
+    G = _avg_split(x.shape[1], nperseg, noverlap, navg)[1]
+    K = _bispec_bins(nperseg // 2 + 1, nbins)
+    return _avg_fake(x, outputs, (x.shape[0], G, K, K), _BISPEC_DTYPES)
 
 
-def _bispec_spectra_shape(X, navg, nbins):
-    B, T, F = X.shape
-    if T < 1:
-        raise ValueError("the spectra must hold at least one frame")
-    if navg > T:
-        raise ValueError(f"navg = {navg} exceeds the number of frames ({T})")
-    return B, _sp_groups(T, navg), _bispec_bins(F, nbins), _bispec_bins(F, nbins)
-
-
-def _bispec_spectra_check(X, Y, Z):
-    for name, v in (("X", X), ("Y", Y), ("Z", Z)):
-        if v is not None and (v.dim() != 3 or v.dtype != torch.complex64
-                              or not v.is_contiguous()):
-            raise ValueError(f"{name} must be contiguous complex64 [batch, frames, F]")
-        if v is not None and (v.shape != X.shape or v.device != X.device):
-            raise ValueError("X, Y and Z must have the same shape and device")
-    if not 1 <= X.shape[2] <= 2049:
-        raise ValueError(f"F must be in [1, 2049], got {X.shape[2]}")
-
-
-def _bispectrum_spectra_out(X, Y, Z, navg, nbins, bispec, bicoh):
-    _bispec_spectra_check(X, Y, Z)
-    shape = _bispec_spectra_shape(X, navg, nbins)
-    _bispec_outputs((bispec, bicoh), shape, X.device)
-    B, T, F = X.shape
+def _bispectrum_spectra_call(X, Y, Z, navg, nbins, outs, mask):
+    B, T, F, G = _avg_spectra((("X", X), ("Y", Y), ("Z", Z)), navg)
+    K = _bispec_bins(F, nbins)
+    outs = _avg_outs(X, outs, mask, (B, G, K, K), _BISPEC_DTYPES, _BISPEC_OUTS)
     same = X.data_ptr()  # the same spectra under another tensor: the auto case
     _lib.check(_lib.lib().specenh_bispectrum_spectra(
         _vp(X), _vp(None if Y is None or Y.data_ptr() == same else Y),
-        _vp(None if Z is None or Z.data_ptr() == same else Z), B, T, F, int(navg), shape[2],
-        _vp(bispec), _vp(bicoh), _st(X)), "bispectrum_spectra")
+        _vp(None if Z is None or Z.data_ptr() == same else Z), B, T, F, int(navg), K,
+        _vp(outs[0]), _vp(outs[1]), _st(X)), "bispectrum_spectra")
+    return outs
+
+
+def _bispectrum_spectra_out(X, Y, Z, navg, nbins, bispec, bicoh):
+    _bispectrum_spectra_call(X, Y, Z, navg, nbins, (bispec, bicoh), 0)
 
 
 def _bispectrum_spectra(X, Y, Z, navg, nbins, outputs):
-    _bispec_spectra_check(X, Y, Z)
-    if not outputs & 3:
-        raise ValueError("no output requested")
-    shape = _bispec_spectra_shape(X, navg, nbins)
-    outs = [torch.empty(shape, dtype=dt, device=X.device) if outputs >> i & 1 else None
-            for i, dt in enumerate(_BISPEC_DTYPES)]
-    _bispectrum_spectra_out(X, Y, Z, navg, nbins, *outs)
-    return tuple(X.new_empty((0,), dtype=dt) if o is None else o
-                 for o, dt in zip(outs, _BISPEC_DTYPES))
+    return _avg_results(X, _bispectrum_spectra_call(X, Y, Z, navg, nbins, None, outputs),
+                        _BISPEC_DTYPES)
 
 
 def _bispectrum_spectra_fake(X, Y, Z, navg, nbins, outputs):
-    shape = _bispec_spectra_shape(X, navg, nbins)
-    return tuple(X.new_empty(shape if outputs >> i & 1 else (0,), dtype=dt)
-                 for i, dt in enumerate(_BISPEC_DTYPES))
+    B, _, F, G = _avg_spectra((("X", X), ("Y", Y), ("Z", Z)), navg)
+    K = _bispec_bins(F, nbins)
+    return _avg_fake(X, outputs, (B, G, K, K), _BISPEC_DTYPES)
 
 
 _op(f"bispectrum(Tensor x, Tensor? y, Tensor? z, {_SP_ARGS}, int nbins, int outputs) -> "
@@ -650,107 +624,72 @@ def _wn_nk(nk):
     return nk
 
 
-def _wn_check(x, y, nperseg, noverlap, navg):
-    _bispec_check(x, y, None, nperseg, noverlap, navg)
-
-
-def _wn_shape(x, nperseg, noverlap, navg, nk):
-    T = (x.shape[1] - nperseg) // (nperseg - noverlap) + 1
-    return x.shape[0], _sp_groups(T, navg), nperseg // 2 + 1, _wn_nk(nk)
-
-
-def _wn_distinct(x, y):
-    """1 when y is x in pointer and stride, else 2, as specenh_wavenumber_spectrum counts."""
-    return _bispec_distinct(x, y, None)
-
-
-def _wn_need(x, nsig, nperseg, noverlap, window, fs, scaling, detrend, navg):
-    from . import stft
-    plan = stft.get_plan_key(x.device, nperseg, noverlap, window, fs, scaling, detrend, 0.0)
-    B, L = x.shape
-    need = int(_lib.lib().specenh_wavenumber_workspace_bytes(plan.handle, B, nsig, L, int(navg)))
-    if need == 0 and B > 0:
-        _lib.check(_lib.SPECENH_EINVAL, "wavenumber_workspace_bytes")
-    return plan, need
-
-
 def wavenumber_workspace(x, y, nperseg, noverlap, window, fs, scaling, detrend, navg):
     """A workspace for ``wavenumber_spectrum_out`` on ``x[B, L]`` and ``y`` (uint8, from torch's
     caching allocator): the spectra of every frame that enters a group of every distinct
     signal, ``8 B nsignals T F`` bytes."""
-    _wn_check(x, y, nperseg, noverlap, navg)
-    _, need = _wn_need(x, _wn_distinct(x, y), nperseg, noverlap, window, fs, scaling, detrend,
-                       navg)
-    return torch.empty(max(need, 1), dtype=torch.uint8, device=x.device)
+    _avg_check((("x", x), ("y", y)), nperseg, noverlap, navg)
+    _, need = _avg_plan(x, (nperseg, noverlap, window, fs, scaling, detrend),
+                        "wavenumber_workspace_bytes", x.shape[0],
+                        _avg_distinct((x, y), (_avg_stride(x), _avg_stride(y))), x.shape[1],
+                        int(navg))
+    return _avg_buffer(need, x.device)
 
 
-def _wn_output(skf, shape, device):
-    if (tuple(skf.shape) != shape or skf.dtype != torch.float32 or not skf.is_contiguous()
-            or skf.device != device):
-        raise ValueError(f"skf must be contiguous float32 {shape} on x's device")
+def _wavenumber_spectrum_call(x, y, p, navg, nk, skf, workspace):
+    """skf None: allocated. Returns it."""
+    _, G = _avg_check((("x", x), ("y", y)), p[0], p[1], navg)
+    B, L = x.shape
+    K = _wn_nk(nk)
+    skf, = _avg_outs(x, None if skf is None else (skf,), 1, (B, G, p[0] // 2 + 1, K), _F32,
+                     "skf float32")
+    strides = (_avg_stride(x), _avg_stride(y))
+    plan, need = _avg_plan(x, p, "wavenumber_workspace_bytes", B, _avg_distinct((x, y), strides),
+                           L, int(navg))
+    ws, nbytes = _avg_workspace(workspace, need, x.device)
+    _lib.check(_lib.lib().specenh_wavenumber_spectrum(
+        plan.handle, _vp(x), _vp(y), B, L, *strides, int(navg), K, _vp(skf), _vp(ws), nbytes,
+        _st(x)), "wavenumber_spectrum")
+    return skf
 
 
 def _wavenumber_spectrum_out(x, y, nperseg, noverlap, window, fs, scaling, detrend, navg, nk,
                              skf, workspace):
-    _wn_check(x, y, nperseg, noverlap, navg)
-    shape = _wn_shape(x, nperseg, noverlap, navg, nk)
-    _wn_output(skf, shape, x.device)
-    plan, need = _wn_need(x, _wn_distinct(x, y), nperseg, noverlap, window, fs, scaling, detrend,
-                          navg)
-    if workspace is None:
-        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=x.device)
-    if (workspace.device != x.device or not workspace.is_contiguous()
-            or workspace.numel() * workspace.element_size() < need or workspace.data_ptr() % 16):
-        raise ValueError(f"workspace must be a contiguous, 16-byte aligned buffer of at least "
-                         f"{need} bytes on x's device")
-    B, L = x.shape
-    _lib.check(_lib.lib().specenh_wavenumber_spectrum(
-        plan.handle, _vp(x), _vp(y), B, L, _bispec_stride(x), _bispec_stride(y), int(navg),
-        shape[3], _vp(skf), _vp(workspace), workspace.numel() * workspace.element_size(),
-        _st(x)), "wavenumber_spectrum")
+    _wavenumber_spectrum_call(x, y, (nperseg, noverlap, window, fs, scaling, detrend), navg, nk,
+                              skf, workspace)
 
 
 def _wavenumber_spectrum(x, y, nperseg, noverlap, window, fs, scaling, detrend, navg, nk):
-    _wn_check(x, y, nperseg, noverlap, navg)
-    skf = torch.empty(_wn_shape(x, nperseg, noverlap, navg, nk), dtype=torch.float32,
-                      device=x.device)
-    _wavenumber_spectrum_out(x, y, nperseg, noverlap, window, fs, scaling, detrend, navg, nk, skf,
-                             None)
-    return skf
+    return _wavenumber_spectrum_call(x, y, (nperseg, noverlap, window, fs, scaling, detrend), navg,
+                                     nk, None, None)
 
 
 def _wavenumber_spectrum_fake(x, y, nperseg, noverlap, window, fs, scaling, detrend, navg, nk):
-    return x.new_empty(_wn_shape(x, nperseg, noverlap, navg, nk), dtype=torch.float32)
+    G = _avg_split(x.shape[1], nperseg, noverlap, navg)[1]
+    return x.new_empty((x.shape[0], G, nperseg // 2 + 1, _wn_nk(nk)), dtype=torch.float32)
 
 
 def _wn_spectra_shape(X, Y, navg, nk):
-    for name, v in (("X", X), ("Y", Y)):
-        if v.dim() != 3 or v.dtype != torch.complex64 or not v.is_contiguous():
-            raise ValueError(f"{name} must be contiguous complex64 [batch, frames, F]")
-    if Y.shape != X.shape or Y.device != X.device:
-        raise ValueError("X and Y must have the same shape and device")
-    B, T, F = X.shape
-    if not 1 <= F <= 2049:
-        raise ValueError(f"F must be in [1, 2049], got {F}")
-    if T < 1:
-        raise ValueError("the spectra must hold at least one frame")
-    if navg > T:
-        raise ValueError(f"navg = {navg} exceeds the number of frames ({T})")
-    return B, _sp_groups(T, navg), F, _wn_nk(nk)
+    B, _, F, G = _avg_spectra((("X", X), ("Y", Y)), navg)
+    return B, G, F, _wn_nk(nk)
+
+
+def _wavenumber_spectra_call(X, Y, navg, nk, skf):
+    """skf None: allocated. Returns it."""
+    shape = _wn_spectra_shape(X, Y, navg, nk)
+    skf, = _avg_outs(X, None if skf is None else (skf,), 1, shape, _F32, "skf float32")
+    _lib.check(_lib.lib().specenh_wavenumber_spectra(
+        _vp(X), _vp(Y), X.shape[0], X.shape[1], X.shape[2], int(navg), shape[3], _vp(skf),
+        _st(X)), "wavenumber_spectra")
+    return skf
 
 
 def _wavenumber_spectra_out(X, Y, navg, nk, skf):
-    shape = _wn_spectra_shape(X, Y, navg, nk)
-    _wn_output(skf, shape, X.device)
-    B, T, F = X.shape
-    _lib.check(_lib.lib().specenh_wavenumber_spectra(
-        _vp(X), _vp(Y), B, T, F, int(navg), shape[3], _vp(skf), _st(X)), "wavenumber_spectra")
+    _wavenumber_spectra_call(X, Y, navg, nk, skf)
 
 
 def _wavenumber_spectra(X, Y, navg, nk):
-    skf = torch.empty(_wn_spectra_shape(X, Y, navg, nk), dtype=torch.float32, device=X.device)
-    _wavenumber_spectra_out(X, Y, navg, nk, skf)
-    return skf
+    return _wavenumber_spectra_call(X, Y, navg, nk, None)
 
 
 def _wavenumber_spectra_fake(X, Y, navg, nk):
@@ -779,20 +718,7 @@ def _corr_check(x, y, nperseg, noverlap, navg, maxlag, mode):
         raise ValueError(f"maxlag must be in [0, nperseg - 1], got {maxlag}")
     if mode not in (_lib.CORR_RAW, _lib.CORR_COEFF):
         raise ValueError(f"mode must be {_lib.CORR_RAW} (raw) or {_lib.CORR_COEFF} (coeff)")
-    _bispec_check(x, y, None, nperseg, noverlap, navg)
-
-
-def _corr_shape(x, nperseg, noverlap, navg, maxlag):
-    T = (x.shape[1] - nperseg) // (nperseg - noverlap) + 1
-    return x.shape[0], _sp_groups(T, navg), 2 * int(maxlag) + 1
-
-
-def _corr_need(x, nperseg, noverlap, window, fs, scaling, detrend, navg, maxlag):
-    from . import stft
-    plan = stft.get_plan_key(x.device, nperseg, noverlap, window, fs, scaling, detrend, 0.0)
-    B, L = x.shape
-    return plan, int(_lib.lib().specenh_correlation_workspace_bytes(plan.handle, B, L, int(navg),
-                                                                    int(maxlag)))
+    return _avg_check((("x", x), ("y", y)), nperseg, noverlap, navg)
 
 
 def correlation_workspace(x, y, nperseg, noverlap, window, fs, scaling, detrend, navg, maxlag):
@@ -800,48 +726,46 @@ def correlation_workspace(x, y, nperseg, noverlap, window, fs, scaling, detrend,
     allocator; one byte when none is needed): one record of ``8 (nperseg + 3)`` bytes per chunk
     of 32 frames when a group is longer than a chunk."""
     _corr_check(x, y, nperseg, noverlap, navg, maxlag, _lib.CORR_RAW)
-    _, need = _corr_need(x, nperseg, noverlap, window, fs, scaling, detrend, navg, maxlag)
-    return torch.empty(max(need, 1), dtype=torch.uint8, device=x.device)
+    _, need = _avg_plan(x, (nperseg, noverlap, window, fs, scaling, detrend),
+                        "correlation_workspace_bytes", x.shape[0], x.shape[1], int(navg),
+                        int(maxlag), may_be_zero=True)
+    return _avg_buffer(need, x.device)
+
+
+def _correlation_call(x, y, p, navg, maxlag, mode, outs, workspace):
+    """outs: (out, energies or None), or None: both are allocated. Returns them."""
+    _, G = _corr_check(x, y, p[0], p[1], navg, maxlag, mode)
+    B, L = x.shape
+    shape = (B, G, 2 * int(maxlag) + 1)
+    out, = _avg_outs(x, outs and outs[:1], 1, shape, _F32, "out float32")
+    energies = None
+    if outs is None or outs[1] is not None:  # energies are optional for the caller's buffers
+        energies, = _avg_outs(x, outs and outs[1:], 1, shape[:2] + (2,), _F32,
+                              "energies float32")
+    plan, need = _avg_plan(x, p, "correlation_workspace_bytes", B, L, int(navg), int(maxlag),
+                           may_be_zero=True)
+    ws, nbytes = _avg_workspace(workspace, need, x.device)
+    _lib.check(_lib.lib().specenh_correlation(
+        plan.handle, _vp(x), _vp(y), B, L, _avg_stride(x), _avg_stride(y), int(navg), int(maxlag),
+        int(mode), _vp(out), _vp(energies), _vp(ws), nbytes, _st(x)), "correlation")
+    return out, energies
 
 
 def _correlation_out(x, y, nperseg, noverlap, window, fs, scaling, detrend, navg, maxlag, mode,
                      out, energies, workspace):
-    _corr_check(x, y, nperseg, noverlap, navg, maxlag, mode)
-    shape = _corr_shape(x, nperseg, noverlap, navg, maxlag)
-    for o, sh, name in ((out, shape, "out"), (energies, shape[:2] + (2,), "energies")):
-        if o is not None and (tuple(o.shape) != sh or o.dtype != torch.float32
-                              or not o.is_contiguous() or o.device != x.device):
-            raise ValueError(f"{name} must be contiguous float32 {sh} on x's device")
-    plan, need = _corr_need(x, nperseg, noverlap, window, fs, scaling, detrend, navg, maxlag)
-    if need and workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
-    if need and (workspace.device != x.device or not workspace.is_contiguous()
-                 or workspace.numel() * workspace.element_size() < need
-                 or workspace.data_ptr() % 16):
-        raise ValueError(f"workspace must be a contiguous, 16-byte aligned buffer of at least "
-                         f"{need} bytes on x's device")
-    B, L = x.shape
-    _lib.check(_lib.lib().specenh_correlation(
-        plan.handle, _vp(x), _vp(y), B, L, _bispec_stride(x), _bispec_stride(y), int(navg),
-        int(maxlag), int(mode), _vp(out), _vp(energies), _vp(workspace if need else None),
-        workspace.numel() * workspace.element_size() if need else 0, _st(x)), "correlation")
+    _correlation_call(x, y, (nperseg, noverlap, window, fs, scaling, detrend), navg, maxlag, mode,
+                      (out, energies), workspace)
 
 
 def _correlation(x, y, nperseg, noverlap, window, fs, scaling, detrend, navg, maxlag, mode):
-    _corr_check(x, y, nperseg, noverlap, navg, maxlag, mode)
-    shape = _corr_shape(x, nperseg, noverlap, navg, maxlag)
-    out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    energies = torch.empty(shape[:2] + (2,), dtype=torch.float32, device=x.device)
-    _correlation_out(x, y, nperseg, noverlap, window, fs, scaling, detrend, navg, maxlag, mode,
-                     out, energies, None)
-    return out, energies
+    return _correlation_call(x, y, (nperseg, noverlap, window, fs, scaling, detrend), navg, maxlag,
+                             mode, None, None)
 
 
 def _correlation_fake(x, y, nperseg, noverlap, window, fs, scaling, detrend, navg, maxlag, mode):
-    _corr_check(x, y, nperseg, noverlap, navg, maxlag, mode)
-    shape = _corr_shape(x, nperseg, noverlap, navg, maxlag)
-    return (x.new_empty(shape, dtype=torch.float32),
-            x.new_empty(shape[:2] + (2,), dtype=torch.float32))
+    _, G = _corr_check(x, y, nperseg, noverlap, navg, maxlag, mode)
+    return (x.new_empty((x.shape[0], G, 2 * int(maxlag) + 1), dtype=torch.float32),
+            x.new_empty((x.shape[0], G, 2), dtype=torch.float32))
 
 
 # the schema calls the mode `normalize`: torch's functionalisation of a mutable operator passes

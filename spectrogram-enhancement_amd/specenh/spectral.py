@@ -53,15 +53,54 @@ def group_times(length: int, nperseg: int, noverlap: int, fs: float, navg=None) 
     return (nperseg / 2 + (np.arange(G, dtype=np.float64) * n + (n - 1) / 2) * hop) / float(fs)
 
 
-def _signals(x, y):
-    for name, v in (("x", x), ("y", y)):
-        if v is not None and not isinstance(v, torch.Tensor):
+# ---------------------------------------------------------------- the averaging wrappers' prologue
+# Shared with specenh.bispectrum, specenh.wavenumber and specenh.correlation, in the order the
+# wrappers check: plan arguments, tensors, frames and groups, and last the device.
+def _plan_args(nperseg, noverlap, scaling, detrend):
+    """(nperseg, noverlap, scaling code, detrend code), normalised as scipy's arguments."""
+    nperseg, noverlap = _check_nperseg(nperseg, noverlap)
+    return nperseg, noverlap, _norm_scaling(scaling), _norm_detrend(detrend)
+
+
+def _names(sig):
+    return ", ".join(list(sig)[:-1]) + " and " + list(sig)[-1]
+
+
+def _signals(need_all=False, **sig):
+    """Tensors by name, each (unless None, where that is allowed) of the first one's shape and
+    device, [batch, length] or [length]; whether they are 1-D."""
+    first, x = next(iter(sig.items()))
+    for name, v in sig.items():
+        if not isinstance(v, torch.Tensor) and (need_all or v is not None):
             raise TypeError(f"{name} must be a torch.Tensor")
     if x.dim() not in (1, 2):
-        raise ValueError("x must be [batch, length]")
-    if y is not None and (y.shape != x.shape or y.device != x.device):
-        raise ValueError("x and y must have the same shape and device")
+        raise ValueError(f"{first} must be [batch, length]")
+    for v in sig.values():
+        if v is not None and (v.shape != x.shape or v.device != x.device):
+            raise ValueError(f"{_names(sig)} must have the same shape and device")
     return x.dim() == 1
+
+
+def _groups(L, nperseg, noverlap, navg):
+    """(navg as an int, frames, groups) of signals of L samples."""
+    if L < nperseg:
+        raise ValueError(f"signal of {L} samples is shorter than nperseg = {nperseg}")
+    navg = int(navg or 0)
+    T = (L - nperseg) // (nperseg - noverlap) + 1
+    if navg > T:
+        raise ValueError(f"navg = {navg} exceeds the number of frames ({T})")
+    return navg, T, (1 if navg <= 0 else T // navg)
+
+
+def _gpu_only(t, module, what="signals"):
+    if t.device.type != "cuda":
+        raise RuntimeError(f"specenh.{module} runs on the GPU only (no CPU fallback); "
+                           f"move the {what} to a ROCm device first")
+
+
+def _same(a, b):
+    return (a.data_ptr() == b.data_ptr() and a.shape == b.shape and a.stride() == b.stride()
+            and a.dtype == b.dtype)
 
 
 def _prep(v):
@@ -70,6 +109,64 @@ def _prep(v):
     if v.dtype != torch.float32:
         v = v.float()
     return v if v.stride(1) == 1 else v.contiguous()
+
+
+def _spectra(need_all=False, **sig):
+    """Complex spectra by name, each (unless None, where that is allowed) like the first,
+    [batch, frames, F] or [frames, F]: (whether 2-D, frames, F, prep); prep(v) is v as the
+    operators take it."""
+    first, X = next(iter(sig.items()))
+    for name, v in sig.items():
+        if not isinstance(v, torch.Tensor) and (need_all or v is not None):
+            raise TypeError(f"{name} must be a torch.Tensor")
+    if not X.is_complex() or X.dim() not in (2, 3):
+        raise ValueError(f"{first} must be complex [batch, frames, F]")
+    for v in sig.values():
+        if v is not None and (v.shape != X.shape or v.device != X.device or not v.is_complex()):
+            raise ValueError(f"{_names(sig)} must be complex and have the same shape and device")
+    squeeze = X.dim() == 2
+    T, F = X.shape[-2], X.shape[-1]
+    if not 1 <= F <= 2049:
+        raise ValueError(f"F must be in [1, 2049], got {F}")
+
+    def prep(v):
+        v = v.unsqueeze(0) if squeeze else v
+        return v.to(torch.complex64).contiguous()
+
+    return squeeze, T, F, prep
+
+
+def _spectra_groups(T, navg):
+    """navg as an int, checked against the T frames of spectra."""
+    navg = int(navg or 0)
+    if T < 1:
+        raise ValueError("the spectra must hold at least one frame")
+    if navg > T:
+        raise ValueError(f"navg = {navg} exceeds the number of frames ({T})")
+    return navg
+
+
+def _capped(B, cap, one_shot, other_bytes=0):
+    """Cuts a batch of B shots into launches whose workspace stays under `cap` bytes (a single
+    shot above it still runs alone): yields (cut, workspace), the workspace shared by the
+    launches; cut(v) is the launch's shots of v[B, ...] (v itself when the launch is the whole
+    batch; None stays None). `one_shot()` is the operator's own ``*_workspace`` for one shot; a
+    workspace is linear in the batch, and one byte says that none is needed: then the batch is
+    one launch. `other_bytes`: what else a shot of a launch holds under the cap."""
+    if not B:
+        return
+    ws = one_shot()
+    per_shot = ws.numel() if ws.numel() > 1 else 0
+    step = B
+    if per_shot or other_bytes:
+        step = min(B, max(1, int(cap) // max(per_shot, other_bytes)))
+    if per_shot and step > 1:
+        ws = ws.new_empty(per_shot * step)
+    if step == B:  # one launch: the tensors as they are, no views
+        yield (lambda v: v), ws
+        return
+    for b0 in range(0, B, step):
+        yield (lambda v, b0=b0: None if v is None else v[b0:b0 + step]), ws
 
 
 def spectral_estimates(x: torch.Tensor, y: torch.Tensor | None = None, fs: float = 1.0,
@@ -91,24 +188,16 @@ def spectral_estimates(x: torch.Tensor, y: torch.Tensor | None = None, fs: float
         if average == "median":
             raise NotImplementedError("average='median' is not supported on the GPU path")
         raise ValueError(f"average must be 'median' or 'mean', got {average}")
-    nperseg, noverlap = _check_nperseg(nperseg, noverlap)
-    sc, dt = _norm_scaling(scaling), _norm_detrend(detrend)
-    squeeze = _signals(x, y)
+    nperseg, noverlap, sc, dt = _plan_args(nperseg, noverlap, scaling, detrend)
+    squeeze = _signals(x=x, y=y)
     want = tuple(want)
     if not want or any(w not in _BITS for w in want):
         raise ValueError(f"want must name some of {tuple(_BITS)}, got {want}")
     if y is None and any(w != "pxx" for w in want):
         raise ValueError("pyy, pxy and coh need a second signal y")
     L = x.shape[-1]
-    if L < nperseg:
-        raise ValueError(f"signal of {L} samples is shorter than nperseg = {nperseg}")
-    navg = int(navg or 0)
-    T = (L - nperseg) // (nperseg - noverlap) + 1
-    if navg > T:
-        raise ValueError(f"navg = {navg} exceeds the number of frames ({T})")
-    if x.device.type != "cuda":
-        raise RuntimeError("specenh.spectral runs on the GPU only (no CPU fallback); "
-                           "move the signals to a ROCm device first")
+    navg, _, _ = _groups(L, nperseg, noverlap, navg)
+    _gpu_only(x, "spectral")
     mask = 0
     for w in want:
         mask |= _BITS[w]
@@ -150,6 +239,18 @@ _CSM_BITS = {"csm": _lib.CSM_CSM, "coh": _lib.CSM_COH}
 CSM_WORKSPACE_CAP = _lib.CSM_WORKSPACE_CAP
 
 
+def _array(x):
+    """x[batch, channels, length] or [channels, length] of 2 to 64 channels; whether 2-D."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("x must be a torch.Tensor")
+    if x.dim() not in (2, 3):
+        raise ValueError("x must be [batch, channels, length] or [channels, length]")
+    if not 2 <= x.shape[-2] <= _lib.CSM_MAX_CHANNELS:
+        raise ValueError(f"channels must be in [2, {_lib.CSM_MAX_CHANNELS}], got {x.shape[-2]} "
+                         "(one channel: welch)")
+    return x.dim() == 2
+
+
 def _prep_array(x):
     if x.dim() == 2:
         x = x.unsqueeze(0)
@@ -175,43 +276,22 @@ def cross_spectral_matrix(x: torch.Tensor, fs: float = 1.0, window="hann", npers
     ``2 <= C <= 64``. ``x[C, L]`` gives ``[F, G, C, C]``.
     """
     from .ops import ops, csm_workspace, window_key
-    nperseg, noverlap = _check_nperseg(nperseg, noverlap)
-    sc, dt = _norm_scaling(scaling), _norm_detrend(detrend)
-    if not isinstance(x, torch.Tensor):
-        raise TypeError("x must be a torch.Tensor")
-    if x.dim() not in (2, 3):
-        raise ValueError("x must be [batch, channels, length] or [channels, length]")
-    squeeze = x.dim() == 2
+    nperseg, noverlap, sc, dt = _plan_args(nperseg, noverlap, scaling, detrend)
+    squeeze = _array(x)
     want = tuple(want)
     if not want or any(w not in _CSM_BITS for w in want):
         raise ValueError(f"want must name some of {tuple(_CSM_BITS)}, got {want}")
     C, L = x.shape[-2], x.shape[-1]
-    if not 2 <= C <= _lib.CSM_MAX_CHANNELS:
-        raise ValueError(f"channels must be in [2, {_lib.CSM_MAX_CHANNELS}], got {C} "
-                         "(one channel: welch)")
-    if L < nperseg:
-        raise ValueError(f"signal of {L} samples is shorter than nperseg = {nperseg}")
-    navg = int(navg or 0)
-    T = (L - nperseg) // (nperseg - noverlap) + 1
-    if navg > T:
-        raise ValueError(f"navg = {navg} exceeds the number of frames ({T})")
-    if x.device.type != "cuda":
-        raise RuntimeError("specenh.spectral runs on the GPU only (no CPU fallback); "
-                           "move the signals to a ROCm device first")
+    navg, _, G = _groups(L, nperseg, noverlap, navg)
+    _gpu_only(x, "spectral")
     x = _prep_array(x)
     B = x.shape[0]
-    G = 1 if navg <= 0 else T // navg
-    key = window_key(window, nperseg)
-    args = (nperseg, noverlap, key, float(fs), sc, dt, navg)
+    args = (nperseg, noverlap, window_key(window, nperseg), float(fs), sc, dt, navg)
     shape = (B, nperseg // 2 + 1, G, C, C)
     outs = [torch.empty(shape, dtype=d, device=x.device) if w in want else None
             for w, d in (("csm", torch.complex64), ("coh", torch.float32))]
-    per_shot = 8 * shape[1] * G * (navg if navg >= 1 else T) * C  # workspace bytes a shot
-    step = max(1, int(CSM_WORKSPACE_CAP) // per_shot)
-    ws = csm_workspace(x[:min(step, B)], *args) if B else None
-    for b0 in range(0, B, step):
-        b1 = min(B, b0 + step)
-        ops.csm_out(x[b0:b1], *args, *(None if o is None else o[b0:b1] for o in outs), ws)
+    for cut, ws in _capped(B, CSM_WORKSPACE_CAP, lambda: csm_workspace(x[:1], *args)):
+        ops.csm_out(cut(x), *args, cut(outs[0]), cut(outs[1]), ws)
     est = {w: (o[0] if squeeze else o) for w, o in zip(("csm", "coh"), outs) if o is not None}
     return frequencies(nperseg, fs), group_times(L, nperseg, noverlap, fs, navg), est
 
@@ -249,9 +329,7 @@ def hermitian_modes(S: torch.Tensor, k: int = 1, return_sweeps: bool = False):
     k = int(k)
     if not 0 <= k <= n:
         raise ValueError(f"k must be in [0, {n}], got {k}")
-    if S.device.type != "cuda":
-        raise RuntimeError("specenh.spectral runs on the GPU only (no CPU fallback); "
-                           "move the matrices to a ROCm device first")
+    _gpu_only(S, "spectral", "matrices")
     if S.dtype != torch.complex64:
         S = S.to(torch.complex64)
     lead = tuple(S.shape[:-2])
@@ -277,45 +355,28 @@ def array_modes(x: torch.Tensor, k: int = 1, fs: float = 1.0, window="hann", npe
     ``power[..., :k] / power.sum(-1)`` (0/0 is NaN). ``1 <= k <= C``. ``x[C, L]`` drops ``B``.
     """
     from .ops import ops, csm_workspace, window_key
-    nperseg, noverlap = _check_nperseg(nperseg, noverlap)
-    sc, dt = _norm_scaling(scaling), _norm_detrend(detrend)
-    if not isinstance(x, torch.Tensor):
-        raise TypeError("x must be a torch.Tensor")
-    if x.dim() not in (2, 3):
-        raise ValueError("x must be [batch, channels, length] or [channels, length]")
-    squeeze = x.dim() == 2
+    nperseg, noverlap, sc, dt = _plan_args(nperseg, noverlap, scaling, detrend)
+    squeeze = _array(x)
     C, L = x.shape[-2], x.shape[-1]
-    if not 2 <= C <= _lib.CSM_MAX_CHANNELS:
-        raise ValueError(f"channels must be in [2, {_lib.CSM_MAX_CHANNELS}], got {C} "
-                         "(one channel: welch)")
     k = int(k)
     if not 1 <= k <= C:
         raise ValueError(f"k must be in [1, {C}], got {k}")
-    if L < nperseg:
-        raise ValueError(f"signal of {L} samples is shorter than nperseg = {nperseg}")
-    navg = int(navg or 0)
-    T = (L - nperseg) // (nperseg - noverlap) + 1
-    if navg > T:
-        raise ValueError(f"navg = {navg} exceeds the number of frames ({T})")
-    if x.device.type != "cuda":
-        raise RuntimeError("specenh.spectral runs on the GPU only (no CPU fallback); "
-                           "move the signals to a ROCm device first")
+    navg, _, G = _groups(L, nperseg, noverlap, navg)
+    _gpu_only(x, "spectral")
     x = _prep_array(x)
-    B = x.shape[0]
-    F, G = nperseg // 2 + 1, (1 if navg <= 0 else T // navg)
+    B, F = x.shape[0], nperseg // 2 + 1
     args = (nperseg, noverlap, window_key(window, nperseg), float(fs), sc, dt, navg)
     power = torch.empty((B, F, G, C), dtype=torch.float32, device=x.device)
     modes = torch.empty((B, F, G, k, C), dtype=torch.complex64, device=x.device)
-    # bytes a shot: the CSM workspace (spectra of every frame) and the matrices themselves
-    per_shot = max(8 * F * G * (navg if navg >= 1 else T) * C, 8 * F * G * C * C)
-    step = max(1, int(CSM_WORKSPACE_CAP) // per_shot)
-    if B:
-        ws = csm_workspace(x[:min(step, B)], *args)
-        buf = torch.empty((min(step, B), F, G, C, C), dtype=torch.complex64, device=x.device)
-    for b0 in range(0, B, step):
-        b1 = min(B, b0 + step)
-        ops.csm_out(x[b0:b1], *args, buf[:b1 - b0], None, ws)
-        ops.herm_eig_out(buf[:b1 - b0], k, power[b0:b1], modes[b0:b1], None)
+    buf = None  # the matrices of a launch: 8 F G C C bytes a shot, under the cap too
+    for cut, ws in _capped(B, CSM_WORKSPACE_CAP, lambda: csm_workspace(x[:1], *args),
+                           8 * F * G * C * C):
+        shots = cut(x)
+        n = shots.shape[0]
+        if buf is None:  # the first launch is the largest
+            buf = torch.empty((n, F, G, C, C), dtype=torch.complex64, device=x.device)
+        ops.csm_out(shots, *args, buf[:n], None, ws)
+        ops.herm_eig_out(buf[:n], k, cut(power), cut(modes), None)
     est = {"power": power, "modes": modes,
            "fraction": power[..., :k] / power.sum(-1, keepdim=True)}
     if squeeze:

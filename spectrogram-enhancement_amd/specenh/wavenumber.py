@@ -31,9 +31,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from .bispectrum import _same
-from .spectral import _prep, group_times
-from .stft import _check_nperseg, _norm_detrend, _norm_scaling, frequencies
+from .spectral import (_capped, _gpu_only, _groups, _plan_args, _prep, _same, _signals, _spectra,
+                       _spectra_groups, group_times)
+from .stft import frequencies
 
 # One launch's workspace (the spectra of every frame of both signals) stays under this many
 # bytes: the batch is split into several launches, a single shot above it still runs alone.
@@ -64,43 +64,21 @@ def wavenumber_spectrum(x: torch.Tensor, y: torch.Tensor, fs: float = 1.0, windo
     consecutive frames, the leftover frames dropped. 1-D input drops ``B``.
     """
     from .ops import ops, wavenumber_workspace, window_key
-    nperseg, noverlap = _check_nperseg(nperseg, noverlap)
-    sc, dt = _norm_scaling(scaling), _norm_detrend(detrend)
-    for name, v in (("x", x), ("y", y)):
-        if not isinstance(v, torch.Tensor):
-            raise TypeError(f"{name} must be a torch.Tensor")
-    if x.dim() not in (1, 2):
-        raise ValueError("x must be [batch, length]")
-    if y.shape != x.shape or y.device != x.device:
-        raise ValueError("x and y must have the same shape and device")
-    squeeze = x.dim() == 1
+    nperseg, noverlap, sc, dt = _plan_args(nperseg, noverlap, scaling, detrend)
+    squeeze = _signals(True, x=x, y=y)
     K = _nk(nk)
     k = wavenumbers(K, dx)
-    F = nperseg // 2 + 1
     L = x.shape[-1]
-    if L < nperseg:
-        raise ValueError(f"signal of {L} samples is shorter than nperseg = {nperseg}")
-    navg = int(navg or 0)
-    T = (L - nperseg) // (nperseg - noverlap) + 1
-    if navg > T:
-        raise ValueError(f"navg = {navg} exceeds the number of frames ({T})")
-    if x.device.type != "cuda":
-        raise RuntimeError("specenh.wavenumber runs on the GPU only (no CPU fallback); "
-                           "move the signals to a ROCm device first")
+    navg, _, G = _groups(L, nperseg, noverlap, navg)
+    _gpu_only(x, "wavenumber")
     xs = _prep(x)
     ys = xs if _same(y, x) else _prep(y)  # a signal given twice is transformed once
-    nsig = 1 if ys is xs else 2
     B = xs.shape[0]
-    G = 1 if navg <= 0 else T // navg
     args = (nperseg, noverlap, window_key(window, nperseg), float(fs), sc, dt, navg)
-    S = torch.empty((B, G, F, K), dtype=torch.float32, device=x.device)
-    per_shot = 8 * nsig * G * (navg if navg >= 1 else T) * F  # workspace bytes a shot
-    step = max(1, int(CSM_WORKSPACE_CAP) // per_shot)
-    sl = slice(0, min(step, B))
-    ws = wavenumber_workspace(xs[sl], ys[sl], *args) if B else None
-    for b0 in range(0, B, step):
-        sl = slice(b0, min(B, b0 + step))
-        ops.wavenumber_spectrum_out(xs[sl], ys[sl], *args, K, S[sl], ws)
+    S = torch.empty((B, G, nperseg // 2 + 1, K), dtype=torch.float32, device=x.device)
+    for cut, ws in _capped(B, CSM_WORKSPACE_CAP,
+                           lambda: wavenumber_workspace(xs[:1], ys[:1], *args)):
+        ops.wavenumber_spectrum_out(cut(xs), cut(ys), *args, K, cut(S), ws)
     return (frequencies(nperseg, fs), k, group_times(L, nperseg, noverlap, fs, navg),
             S[0] if squeeze else S)
 
@@ -111,31 +89,10 @@ def wavenumber_spectrum_from_spectra(X: torch.Tensor, Y: torch.Tensor, navg=None
     ``w = (|X|^2 + |Y|^2) / 2``. Returns ``S`` float32 ``[B, G, F, K]``; ``X[T, F]`` drops
     ``B``."""
     from .ops import ops
-    for name, v in (("X", X), ("Y", Y)):
-        if not isinstance(v, torch.Tensor):
-            raise TypeError(f"{name} must be a torch.Tensor")
-    if not X.is_complex() or X.dim() not in (2, 3):
-        raise ValueError("X must be complex [batch, frames, F]")
-    if Y.shape != X.shape or Y.device != X.device or not Y.is_complex():
-        raise ValueError("X and Y must be complex and have the same shape and device")
-    squeeze = X.dim() == 2
+    squeeze, T, _, prep = _spectra(True, X=X, Y=Y)
     K = _nk(nk)
-    T, F = X.shape[-2], X.shape[-1]
-    if not 1 <= F <= 2049:
-        raise ValueError(f"F must be in [1, 2049], got {F}")
-    navg = int(navg or 0)
-    if T < 1:
-        raise ValueError("the spectra must hold at least one frame")
-    if navg > T:
-        raise ValueError(f"navg = {navg} exceeds the number of frames ({T})")
-    if X.device.type != "cuda":
-        raise RuntimeError("specenh.wavenumber runs on the GPU only (no CPU fallback); "
-                           "move the spectra to a ROCm device first")
-
-    def prep(v):
-        v = v.unsqueeze(0) if squeeze else v
-        return v.to(torch.complex64).contiguous()
-
+    navg = _spectra_groups(T, navg)
+    _gpu_only(X, "wavenumber", "spectra")
     S = ops.wavenumber_spectra(prep(X), prep(Y), navg, K)
     return S[0] if squeeze else S
 

@@ -20,30 +20,15 @@ Also recorded: the agreement with the torch expression on the coefficient scale 
 kernels' resource usage (-Rpass-analysis=kernel-resource-usage).
     python tools/correlation_bench.py [--json PATH] [--rounds N]"""
 import json
-import os
-import re
-import statistics
-import subprocess
-import sys
-import tempfile
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [REPO, os.path.join(REPO, "spectrogram-enhancement_amd")]
-import torch  # noqa: E402
-from specenh import correlation as co  # noqa: E402
-from specenh import ops as sops  # noqa: E402
-from specenh.synthetic import plasma_chirps_torch  # noqa: E402
+from benchlib import measure, parse_args, resources, write_json  # puts the package on sys.path
 
-args = list(sys.argv[1:])
-path, ROUNDS = None, 11
-for flag in ("--json", "--rounds"):
-    if flag in args:
-        i = args.index(flag)
-        if flag == "--json":
-            path = args[i + 1]
-        else:
-            ROUNDS = int(args[i + 1])
-        del args[i:i + 2]
+import torch
+from specenh import correlation as co
+from specenh import ops as sops
+from specenh.synthetic import plasma_chirps_torch
+
+path, ROUNDS, _ = parse_args(11)
 N, NOV, WIN, FS, L, B, M = 1024, 768, "boxcar", 500000.0, 65536, 64, 256
 HOP = N - NOV
 T = (L - N) // HOP + 1
@@ -51,51 +36,6 @@ WARM, HBM = 3, 8.0e12
 OP = (N, NOV, WIN, FS, 0, 1)  # density (unused), constant detrend
 ops = torch.ops.specenh
 SHAPES = [("B64 navg0", 0), ("B64 navg8", 8)]
-
-
-def resources():
-    """VGPRs, scratch, LDS and occupancy of the kernels, from the compiler."""
-    import build  # spectrogram-enhancement_amd/build.py: the flags the library is built with
-    src = os.path.join(build.CSRC, "correlation.hip")
-    with tempfile.TemporaryDirectory() as tmp:
-        r = subprocess.run([build.HIPCC, *build.CFLAGS, "-Rpass-analysis=kernel-resource-usage",
-                            "-c", src, "-o", os.path.join(tmp, "correlation.o")],
-                           capture_output=True, text=True)
-    out, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark:\s+(?:Function Name: (\S+)|"
-                      r"([A-Za-z][^:\[]*?)(?: \[[^\]]*\])?: (\S+))", line)
-        if not m:
-            continue
-        if m.group(1):
-            name = m.group(1)
-            out[name] = {}
-        elif name:
-            out[name][m.group(2).strip()] = m.group(3)
-    return out or {"error": r.stderr[-500:]}
-
-
-def timed(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
-
-
-def measure(runs):
-    for fn in runs.values():
-        for _ in range(WARM):
-            fn()
-    torch.cuda.synchronize()
-    times = {name: [] for name in runs}
-    for _ in range(ROUNDS):  # interleaved: the routes see the same clock / thermal state
-        for name, fn in runs.items():
-            times[name].append(timed(fn))
-    out = {f"{name}_ms_median": statistics.median(t) for name, t in times.items()}
-    out.update({f"{name}_ms_min": min(t) for name, t in times.items()})
-    return out
 
 
 def torch_rho(x, y, navg):
@@ -119,7 +59,8 @@ def torch_rho(x, y, navg):
 
 res = {"plan": {"nperseg": N, "noverlap": NOV, "window": WIN, "detrend": "constant"},
        "length": L, "frames": T, "maxlag": M, "pairs": B, "rounds": ROUNDS, "warmups": WARM,
-       "hbm_ceiling_bytes_per_s": HBM, "kernel_resources": resources(), "shapes": {}}
+       "hbm_ceiling_bytes_per_s": HBM, "kernel_resources": resources("correlation.hip"),
+       "shapes": {}}
 print(json.dumps(res["kernel_resources"]), flush=True)
 x, y = (plasma_chirps_torch(B, L, seed=s, device="cuda") for s in (1, 2))
 y = 0.7 * torch.roll(x, 3, dims=1) + 0.5 * y  # partly coherent, as the parity tests
@@ -142,7 +83,7 @@ for label, navg in SHAPES:
     entry = {"batch": B, "navg": navg, "groups": G, "frames_used": used,
              "workspace_bytes": int(ws.numel()) if ws.numel() > 1 else 0,
              "output_bytes": out.numel() * 4}
-    entry.update(measure(runs))
+    entry.update(measure(runs, ROUNDS, WARM))
     samples = (used - 1) * HOP + N
     nbytes = B * (2 * samples * 4 + G * (2 * M + 1) * 4 + G * 8)
     entry["algorithmic_bytes"] = nbytes
@@ -172,14 +113,11 @@ for pairs in (4, 16, 32, 64, 128, 256):
     xs, ys = (plasma_chirps_torch(pairs, L, seed=s, device="cuda") for s in (3, 4))
     out = torch.empty((pairs, 1, 2 * M + 1), device="cuda")
     ws = sops.correlation_workspace(xs, ys, *OP, 0, M)
-    m = measure({"correlation": lambda: ops.correlation_out(xs, ys, *OP, 0, M, 1, out, None, ws)})
+    m = measure({"correlation": lambda: ops.correlation_out(xs, ys, *OP, 0, M, 1, out, None, ws)},
+                ROUNDS, WARM)
     res["whole_shot_scaling_us_median"][str(pairs)] = m["correlation_ms_median"] * 1e3
     del xs, ys, out, ws
 print("whole-shot: " + "  ".join(f"{p} pairs {t:7.1f} us"
                                  for p, t in res["whole_shot_scaling_us_median"].items()),
       flush=True)
-print(json.dumps(res))
-if path:
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    with open(path, "w") as fh:
-        json.dump(res, fh, indent=1)
+write_json(res, path)

@@ -7,28 +7,16 @@ split between the two kernels comes from one torch.profiler pass of their own; t
 kernel's rate is the MFMA work it issues (32x32 tiles, padded channels included) and the work
 of the upper triangle alone, over its time, against the 157 TF fp32 peak.
     python tools/csm_bench.py [--json PATH] [--rounds N]"""
-import json
-import os
 import statistics
-import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [REPO, os.path.join(REPO, "spectrogram-enhancement_amd")]
-import torch  # noqa: E402
-from specenh import ops as _ops  # noqa: E402
-from specenh import spectral, stft  # noqa: E402
-from specenh.synthetic import plasma_chirps_torch  # noqa: E402
+from benchlib import parse_args, sample, write_json  # puts the package on sys.path
 
-args = list(sys.argv[1:])
-path, ROUNDS = None, 11
-for flag in ("--json", "--rounds"):
-    if flag in args:
-        i = args.index(flag)
-        if flag == "--json":
-            path = args[i + 1]
-        else:
-            ROUNDS = int(args[i + 1])
-        del args[i:i + 2]
+import torch
+from specenh import ops as _ops
+from specenh import spectral, stft
+from specenh.synthetic import plasma_chirps_torch
+
+path, ROUNDS, _ = parse_args(11)
 N, NOV, WIN, FS = 1024, 768, "hamm", 500000.0
 DENSITY, LINEAR = 0, 2
 WARM, PEAK = 3, 157.0e12
@@ -89,19 +77,7 @@ for label, B, C, L, navg in SHAPES:
                 ops.spectral_mean_out(rows[i], rows[j], *PLAN, navg, None, None, pxy, None, pw)
 
     runs = {"csm": matrix, "pair route": pairs}
-    for fn in runs.values():
-        for _ in range(WARM):
-            fn()
-    torch.cuda.synchronize()
-    times = {k: [] for k in runs}
-    for _ in range(ROUNDS):  # interleaved: both routes see the same clock / thermal state
-        for k, fn in runs.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            e1.synchronize()
-            times[k].append(e0.elapsed_time(e1))
+    times = sample(runs, ROUNDS, WARM)
     # agreement of the two routes on one pair and one diagonal element
     matrix()
     ops.spectral_mean_out(rows[1], rows[C - 1], *PLAN, navg, None, None, pxy, None, pw)
@@ -135,8 +111,4 @@ for label, B, C, L, navg in SHAPES:
           f"  split {split}  workspace {ws.numel() / 1e6:.0f} MB  agree {agree}", flush=True)
     del x, S, K, ws, rows
     torch.cuda.empty_cache()
-print(json.dumps(res))
-if path:
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    with open(path, "w") as fh:
-        json.dump(res, fh, indent=1)
+write_json(res, path)

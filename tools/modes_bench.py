@@ -21,30 +21,16 @@ numpy.linalg.eigh in complex128) and the kernel's resource usage
 (-Rpass-analysis=kernel-resource-usage).
     python tools/modes_bench.py [--json PATH] [--rounds N]"""
 import json
-import os
-import re
 import statistics
-import subprocess
-import sys
-import tempfile
 import time
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [REPO, os.path.join(REPO, "spectrogram-enhancement_amd")]
-import torch  # noqa: E402
-from specenh import _lib, spectral  # noqa: E402
-from specenh.synthetic import plasma_chirps_torch  # noqa: E402
+from benchlib import parse_args, resources, timed, write_json  # puts the package on sys.path
 
-args = list(sys.argv[1:])
-path, ROUNDS = None, 11
-for flag in ("--json", "--rounds"):
-    if flag in args:
-        i = args.index(flag)
-        if flag == "--json":
-            path = args[i + 1]
-        else:
-            ROUNDS = int(args[i + 1])
-        del args[i:i + 2]
+import torch
+from specenh import _lib, spectral
+from specenh.synthetic import plasma_chirps_torch
+
+path, ROUNDS, _ = parse_args(11)
 N, NOV, WIN, FS = 1024, 768, "hamm", 500000.0
 WARM = 3
 EIGH_CALL_S = 4.0
@@ -55,37 +41,6 @@ SHAPES = [("B8 C40 L65536 navg0", 8, 40, 65536, 0),
           ("B8 C40 L65536 navg8", 8, 40, 65536, 8),
           ("B1 C40 L1048576 navg0", 1, 40, 1 << 20, 0),
           ("B8 C4 L65536 navg0", 8, 4, 65536, 0)]
-
-
-def resources():
-    """VGPRs, SGPRs, scratch and occupancy of every herm_eig kernel, from the compiler."""
-    import build  # spectrogram-enhancement_amd/build.py: the flags the library is built with
-    src = os.path.join(build.CSRC, "herm_eig.hip")
-    with tempfile.TemporaryDirectory() as tmp:
-        r = subprocess.run([build.HIPCC, *build.CFLAGS, "-Rpass-analysis=kernel-resource-usage",
-                            "-c", src, "-o", os.path.join(tmp, "herm_eig.o")],
-                           capture_output=True, text=True)
-    out, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark:\s+(?:Function Name: (\S+)|"
-                      r"([A-Za-z][^:\[]*?)(?: \[[^\]]*\])?: (\S+))", line)
-        if not m:
-            continue
-        if m.group(1):
-            name = m.group(1)
-            out[name] = {}
-        elif name:
-            out[name][m.group(2).strip()] = m.group(3)
-    return out or {"error": r.stderr[-500:]}
-
-
-def timed(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
 
 
 def baseline_slice(S):
@@ -122,7 +77,8 @@ def baseline_slice(S):
 
 res = {"plan": {"nperseg": N, "noverlap": NOV, "window": WIN, "detrend": "linear",
                 "scaling": "density"}, "rounds": ROUNDS, "warmups": WARM,
-       "max_sweeps": _lib.HERM_EIG_MAX_SWEEPS, "kernel_resources": resources(), "shapes": {}}
+       "max_sweeps": _lib.HERM_EIG_MAX_SWEEPS, "kernel_resources": resources("herm_eig.hip"),
+       "shapes": {}}
 print(json.dumps(res["kernel_resources"]), flush=True)
 for label, B, C, L, navg in SHAPES:
     x = plasma_chirps_torch(B * C, L, seed=1, device="cuda").reshape(B, C, L)
@@ -197,8 +153,4 @@ for label, B, C, L, navg in SHAPES:
     res["shapes"][label] = entry
     del x, S, w, sw, base
     torch.cuda.empty_cache()
-print(json.dumps(res))
-if path:
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    with open(path, "w") as fh:
-        json.dump(res, fh, indent=1)
+write_json(res, path)

@@ -5,24 +5,16 @@ Welch PSD, and specenh_csd COMPLEX followed by .mean(-1) for the averaged cross 
 both on the device. HIP events around each route, a warm-up, interleaved rounds, median (and
 min) of ROUNDS runs each; algorithmic bytes over the time as a fraction of 8 TB/s.
     python tools/spectral_bench.py [B] [--json PATH]"""
-import json
-import os
 import statistics
-import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [REPO, os.path.join(REPO, "spectrogram-enhancement_amd")]
-import torch  # noqa: E402
-from specenh import ops as _ops  # noqa: E402
-from specenh import spectral, stft  # noqa: E402
-from specenh.synthetic import plasma_chirps_torch  # noqa: E402
+from benchlib import parse_args, sample, write_json  # puts the package on sys.path
 
-args = list(sys.argv[1:])
-path = None
-if "--json" in args:
-    i = args.index("--json")
-    path = args[i + 1]
-    del args[i:i + 2]
+import torch
+from specenh import ops as _ops
+from specenh import spectral, stft
+from specenh.synthetic import plasma_chirps_torch
+
+path, _, args = parse_args()
 B = int(args[0]) if args else 4096
 L, N, NOV, WIN, FS = 65536, 1024, 768, "hamm", 500000.0
 DENSITY, LINEAR = 0, 2
@@ -64,19 +56,7 @@ runs = {
     "spectral_mean pair navg=8": (lambda: ops.spectral_mean_out(x, y, *PLAN, NAVG, *A8, ws8),
                                   2 * sig + 20 * spec * G),
 }
-for fn, _ in runs.values():
-    for _ in range(WARM):
-        fn()
-torch.cuda.synchronize()
-times = {k: [] for k in runs}
-for _ in range(ROUNDS):  # interleaved: every variant sees the same clock / thermal state
-    for k, (fn, _) in runs.items():
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        times[k].append(e0.elapsed_time(e1))
+times = sample({k: fn for k, (fn, _) in runs.items()}, ROUNDS, WARM)
 # the fused results against the routes they replace
 ops.stft_psd_out(x, *PLAN, 1e-11, 0, P)
 ops.spectral_mean_out(x, y, *PLAN, 0, *A0, ws0)
@@ -101,8 +81,4 @@ for k, (_, alg) in runs.items():
           f"{alg / med[k] / 1e6:6.0f} GB/s  frac {alg / (med[k] * 1e-3) / HBM:.3f}  "
           f"x existing route {med[k] / base:.3f}", flush=True)
 print(f"agreement with the existing routes (normwise): {agree}")
-print(json.dumps(res))
-if path:
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    with open(path, "w") as fh:
-        json.dump(res, fh, indent=1)
+write_json(res, path)

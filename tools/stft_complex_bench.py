@@ -3,23 +3,15 @@
 same shape in the same run. HIP events around single launches, a warm-up, interleaved rounds,
 median (and min) of ROUNDS launches each; algorithmic bytes over the time as a fraction of
 8 TB/s.   python tools/stft_complex_bench.py [B] [--json PATH]"""
-import json
-import os
 import statistics
-import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [REPO, os.path.join(REPO, "spectrogram-enhancement_amd")]
-import torch  # noqa: E402
-from specenh import stft  # noqa: E402
-from specenh.synthetic import plasma_chirps_torch  # noqa: E402
+from benchlib import parse_args, sample, write_json  # puts the package on sys.path
 
-args = list(sys.argv[1:])
-path = None
-if "--json" in args:
-    i = args.index("--json")
-    path = args[i + 1]
-    del args[i:i + 2]
+import torch
+from specenh import stft
+from specenh.synthetic import plasma_chirps_torch
+
+path, _, args = parse_args()
 B = int(args[0]) if args else 4096
 L, N, NOV, WIN, FS = 65536, 1024, 768, "hamm", 500000.0
 ROUNDS, WARM, HBM = 25, 3, 8.0e12
@@ -45,19 +37,7 @@ runs = {
     "istft gain[F-1]": (lambda: ops.istft_out(Z, gain, N, NOV, WIN, FS, 1, True, y),
                         B * (8 * F * T + 4 * (F - 1) * T + 4 * n_out)),
 }
-for fn, _ in runs.values():
-    for _ in range(WARM):
-        fn()
-torch.cuda.synchronize()
-times = {k: [] for k in runs}
-for _ in range(ROUNDS):  # interleaved: every variant sees the same clock / thermal state
-    for k, (fn, _) in runs.items():
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        times[k].append(e0.elapsed_time(e1))
+times = sample({k: fn for k, (fn, _) in runs.items()}, ROUNDS, WARM)
 ops.istft_out(Z, None, N, NOV, WIN, FS, 1, True, y)
 rt = float((y[:, :L] - x).abs().max() / x.abs().max())
 res = {"shape": {"batch": B, "length": L, "nperseg": N, "noverlap": NOV, "window": WIN,
@@ -71,8 +51,4 @@ for k, (_, alg) in runs.items():
     print(f"{k:18s} median {med:.4f} ms  min {mn:.4f} ms  {alg / med / 1e6:.0f} GB/s  "
           f"frac {alg / (med * 1e-3) / HBM:.3f}  x psd {med / base:.2f}", flush=True)
 print(f"round trip max|istft(stft(x)) - x| / max|x| = {rt:.2e}")
-print(json.dumps(res))
-if path:
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    with open(path, "w") as fh:
-        json.dump(res, fh, indent=1)
+write_json(res, path)

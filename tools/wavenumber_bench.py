@@ -21,82 +21,22 @@ kernels' resource usage (-Rpass-analysis=kernel-resource-usage).
     python tools/wavenumber_bench.py [--json PATH] [--rounds N]"""
 import json
 import math
-import os
-import re
-import statistics
-import subprocess
-import sys
-import tempfile
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [REPO, os.path.join(REPO, "spectrogram-enhancement_amd")]
-import torch  # noqa: E402
-from specenh import bispectrum as bs  # noqa: E402
-from specenh import stft  # noqa: E402
-from specenh import wavenumber as wn  # noqa: E402
-from specenh.synthetic import plasma_chirps_torch  # noqa: E402
+from benchlib import measure, parse_args, resources, write_json  # puts the package on sys.path
 
-args = list(sys.argv[1:])
-path, ROUNDS = None, 11
-for flag in ("--json", "--rounds"):
-    if flag in args:
-        i = args.index(flag)
-        if flag == "--json":
-            path = args[i + 1]
-        else:
-            ROUNDS = int(args[i + 1])
-        del args[i:i + 2]
+import torch
+from specenh import bispectrum as bs
+from specenh import stft
+from specenh import wavenumber as wn
+from specenh.synthetic import plasma_chirps_torch
+
+path, ROUNDS, _ = parse_args(11)
 N, NOV, WIN, FS, L, B, NK = 1024, 768, "hamm", 500000.0, 65536, 64, 64
 F, T = N // 2 + 1, (L - N) // (N - NOV) + 1
 WARM, HBM = 3, 8.0e12
 KW = dict(fs=FS, window=WIN, nperseg=N, noverlap=NOV, detrend="constant", scaling="density")
 ops = torch.ops.specenh
 SHAPES = [("B64 navg0", 0), ("B64 navg8", 8)]
-
-
-def resources():
-    """VGPRs, scratch, LDS and occupancy of the accumulate kernel, from the compiler."""
-    import build  # spectrogram-enhancement_amd/build.py: the flags the library is built with
-    src = os.path.join(build.CSRC, "wavenumber.hip")
-    with tempfile.TemporaryDirectory() as tmp:
-        r = subprocess.run([build.HIPCC, *build.CFLAGS, "-Rpass-analysis=kernel-resource-usage",
-                            "-c", src, "-o", os.path.join(tmp, "wavenumber.o")],
-                           capture_output=True, text=True)
-    out, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark:\s+(?:Function Name: (\S+)|"
-                      r"([A-Za-z][^:\[]*?)(?: \[[^\]]*\])?: (\S+))", line)
-        if not m:
-            continue
-        if m.group(1):
-            name = m.group(1)
-            out[name] = {}
-        elif name:
-            out[name][m.group(2).strip()] = m.group(3)
-    return out or {"error": r.stderr[-500:]}
-
-
-def timed(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
-
-
-def measure(runs):
-    for fn in runs.values():
-        for _ in range(WARM):
-            fn()
-    torch.cuda.synchronize()
-    times = {name: [] for name in runs}
-    for _ in range(ROUNDS):  # interleaved: the routes see the same clock / thermal state
-        for name, fn in runs.items():
-            times[name].append(timed(fn))
-    out = {f"{name}_ms_median": statistics.median(t) for name, t in times.items()}
-    out.update({f"{name}_ms_min": min(t) for name, t in times.items()})
-    return out
 
 
 def spectra(s):
@@ -127,7 +67,7 @@ def torch_skf(x, y, navg):
 res = {"plan": {"nperseg": N, "noverlap": NOV, "window": WIN, "detrend": "constant",
                 "scaling": "density"}, "length": L, "frames": T, "bins": F, "nk": NK, "pairs": B,
        "rounds": ROUNDS, "warmups": WARM, "hbm_ceiling_bytes_per_s": HBM,
-       "kernel_resources": resources(), "shapes": {}}
+       "kernel_resources": resources("wavenumber.hip"), "shapes": {}}
 print(json.dumps(res["kernel_resources"]), flush=True)
 x, y = (plasma_chirps_torch(B, L, seed=s, device="cuda") for s in (1, 2))
 y = 0.7 * torch.roll(x, 3, dims=1) + 0.5 * y  # partly coherent, as the parity tests
@@ -144,7 +84,7 @@ for label, navg in SHAPES:
             "torch": lambda: torch_skf(x, y, navg)}
     entry = {"batch": B, "navg": navg, "groups": G, "frames_used": used,
              "output_bytes": out.numel() * 4}
-    entry.update(measure(runs))
+    entry.update(measure(runs, ROUNDS, WARM))
     nbytes = B * (2 * used * F * 8 + G * F * NK * 4)
     entry["accumulate_bytes"] = nbytes
     entry["accumulate_bytes_per_s"] = nbytes / (entry["accumulate_ms_median"] * 1e-3)
@@ -176,13 +116,10 @@ for nk in (16, 64, 256):
         X, Y = (torch.view_as_complex(torch.randn(pairs, T, F, 2, device="cuda", generator=gen))
                 for _ in range(2))
         out = torch.empty((pairs, 1, F, nk), device="cuda")
-        m = measure({"accumulate": lambda: ops.wavenumber_spectra_out(X, Y, 0, nk, out)})
+        m = measure({"accumulate": lambda: ops.wavenumber_spectra_out(X, Y, 0, nk, out)},
+                    ROUNDS, WARM)
         row[str(pairs)] = m["accumulate_ms_median"] * 1e3
     res["accumulate_scaling_us_median"][str(nk)] = row
     print(f"accumulate alone, whole-shot, nk {nk:3d}: " +
           "  ".join(f"{p} pairs {t:6.1f} us" for p, t in row.items()), flush=True)
-print(json.dumps(res))
-if path:
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    with open(path, "w") as fh:
-        json.dump(res, fh, indent=1)
+write_json(res, path)
