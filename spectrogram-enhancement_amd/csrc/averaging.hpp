@@ -120,6 +120,14 @@ inline size_t frames_workspace_bytes(const specenh_stft_plan* plan, long long ba
 int transform_frames(const specenh_stft_plan* plan, const FrameSignals& sig, int nsig,
                      long long batch, long long Tu, void* workspace, hipStream_t stream);
 
+// The channel-array form: detrends, windows and transforms frames [0, Tu) of the C channels of
+// nb <= 65535 shots, once, into `ws` as float2 [nb][F][Tu][C] holding 2 X (defined in
+// spectral_matrix.hip beside its kernel; what specenh_csm and specenh_array_spectrum sum).
+// SPECENH_OK or a negative error.
+int csm_transform(const specenh_stft_plan* plan, const float* x, long long nb, int C,
+                  long long channel_stride, long long batch_stride, long long Tu, float2* ws,
+                  hipStream_t stream);
+
 // Spectra the caller holds, [batch][frames][nfreq]: fills *G (groups).
 inline int check_spectra(long long batch, long long frames, long long nfreq, long long navg,
                          long long* G) {

@@ -233,6 +233,29 @@ int split_for(const specenh_stft_plan* plan, long long batch, long long channels
 }
 
 }  // namespace
+
+int csm_transform(const specenh_stft_plan* plan, const float* x, long long nb, int C,
+                  long long channel_stride, long long batch_stride, long long Tu, float2* ws,
+                  hipStream_t stream) {
+  const int N = plan->nperseg;
+  if (Tu * ((C + slots8_for(N) - 1) / slots8_for(N)) > 2147483647LL)
+    return set_error(SPECENH_EUNSUPPORTED, "too many frames");
+  hipError_t e = allow_lds(g_lds, {(const void*)csm_transform_kernel}, MAX_LDS);
+  if (e != hipSuccess)
+    return set_error(SPECENH_EHIP, std::string("csm: ") + hipGetErrorString(e));
+  TransformArgs t{};
+  t.x = x; t.ws = ws;
+  t.bs = batch_stride; t.cs = channel_stride;
+  t.C = C; t.N = N; t.log2n = ilog2i(N); t.hop = plan->hop;
+  t.S = slots8_for(N); t.log2s = ilog2i(t.S); t.detrend = plan->detrend;
+  t.Tu = (int)Tu; t.nblk = (C + t.S - 1) / t.S;
+  t.win = plan->d_window; t.tw = plan->d_tw_nat;
+  const size_t lds = (size_t)t.S * N * sizeof(float2);  // two buffers of S * N/2
+  SPECENH_LAUNCH(csm_transform_kernel, dim3((unsigned)(Tu * t.nblk), 1, (unsigned)nb), dim3(CT),
+                 lds, stream, t);
+  return launched("csm_transform");
+}
+
 }  // namespace specenh
 
 extern "C" {
@@ -267,18 +290,6 @@ int specenh_csm(const specenh_stft_plan* plan, const float* x, long long batch,
   const int ntp = C <= TILE ? 1 : 3;
   const long long per_shot = s.G * F * ntp;  // waves of the Gram kernel
   if (per_shot > (1ll << 31)) return set_error(SPECENH_EUNSUPPORTED, "too many groups");
-  if (s.Tu * ((C + slots8_for(N) - 1) / slots8_for(N)) > 2147483647LL)
-    return set_error(SPECENH_EUNSUPPORTED, "too many frames");
-  hipError_t e = allow_lds(g_lds, {(const void*)csm_transform_kernel}, MAX_LDS);
-  if (e != hipSuccess)
-    return set_error(SPECENH_EHIP, std::string("csm: ") + hipGetErrorString(e));
-  TransformArgs t{};
-  t.bs = batch_stride; t.cs = channel_stride;
-  t.C = C; t.N = N; t.log2n = ilog2i(N); t.hop = plan->hop;
-  t.S = slots8_for(N); t.log2s = ilog2i(t.S); t.detrend = plan->detrend;
-  t.Tu = (int)s.Tu; t.nblk = (C + t.S - 1) / t.S;
-  t.win = plan->d_window; t.tw = plan->d_tw_nat;
-  const size_t lds = (size_t)t.S * N * sizeof(float2);  // two buffers of S * N/2
   GramArgs g{};
   g.C = C; g.F = (int)F; g.G = (int)s.G; g.glen = (int)s.glen; g.Tu = (int)s.Tu; g.ntp = ntp;
   g.m = plan->scale / (4.0 * (double)s.glen);
@@ -288,13 +299,11 @@ int specenh_csm(const specenh_stft_plan* plan, const float* x, long long batch,
   const long long ws_shot = F * s.Tu * C, out_shot = F * s.G * C * C;
   for (long long b0 = 0; b0 < batch; b0 += step) {
     const long long nb = batch - b0 < step ? batch - b0 : step;
-    t.x = x + b0 * batch_stride;
-    t.ws = reinterpret_cast<float2*>(workspace) + b0 * ws_shot;
-    SPECENH_LAUNCH(csm_transform_kernel,
-                   dim3((unsigned)(s.Tu * t.nblk), 1, (unsigned)nb), dim3(CT),
-                   lds, (hipStream_t)stream, t);
-    if (int rc = launched("csm_transform")) return rc;
-    g.ws = t.ws;
+    float2* ws = reinterpret_cast<float2*>(workspace) + b0 * ws_shot;
+    if (int rc = csm_transform(plan, x + b0 * batch_stride, nb, C, channel_stride, batch_stride,
+                               s.Tu, ws, (hipStream_t)stream))
+      return rc;
+    g.ws = ws;
     g.csm = csm ? reinterpret_cast<float2*>(csm) + b0 * out_shot : nullptr;
     g.coh = coh ? coh + b0 * out_shot : nullptr;
     g.waves = nb * per_shot;

@@ -21,6 +21,9 @@ two-point wavenumber-frequency spectrum S(k, f) (dispersion relation from two ch
 block-averaged lagged cross-correlation (time-delay estimation, correlation time):
   specenh.signal.correlate (numpy); specenh.correlation.correlate, autocorrelate,
   correlation_lags, time_delay, correlation_time (device tensors)
+steered-response spectra of a channel array (Bartlett, Capon, MUSIC: mode numbers, wavenumbers):
+  specenh.signal.array_spectrum (numpy); specenh.beamform.array_spectrum,
+  mode_number_spectrum, steered_power, steering_vectors, delay_steering (device tensors)
 Device fast paths: specgr_batch, denoise_batch, cross_spectrogram_batch, and
 specenh.autograd (differentiable Conv2D / Conv2DTranspose / MaxPooling2D / BCE).
 Every one of them reaches the HIP kernels through the ``torch.ops.specenh`` operators

@@ -274,6 +274,27 @@ SIGNATURES_CORRELATION = {
                                        _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
 }
 
+# steered-response spectra (Bartlett, Capon, MUSIC); must match include/specenh_beamform.h
+STEER_MAX_CHANNELS = 64  # SPECENH_STEER_MAX_CHANNELS
+STEER_MAX_NSTEER = 4096  # SPECENH_STEER_MAX_NSTEER
+# SPECENH_STEER_*: the epilogue of the steered-power kernel
+STEER_SUM, STEER_BARTLETT, STEER_INVERSE, STEER_MUSIC = 0, 1, 2, 3
+SIGNATURES_BEAMFORM = {
+    "specenh_steered_power": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_longlong,
+                                         _c.c_longlong, _c.c_longlong, _c.c_longlong,
+                                         _c.c_longlong, _c.c_longlong, _c.c_longlong,
+                                         _c.c_longlong, _c.c_int, _c.c_double, _c.c_void_p,
+                                         _c.c_int, _c.c_void_p, _c.c_void_p]),
+    "specenh_array_spectrum_workspace_bytes": (_c.c_size_t, [_c.c_void_p, _c.c_longlong,
+                                                             _c.c_longlong, _c.c_longlong,
+                                                             _c.c_longlong]),
+    "specenh_array_spectrum": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_longlong,
+                                          _c.c_longlong, _c.c_longlong, _c.c_longlong,
+                                          _c.c_longlong, _c.c_longlong, _c.c_void_p,
+                                          _c.c_longlong, _c.c_int, _c.c_void_p, _c.c_void_p,
+                                          _c.c_size_t, _c.c_void_p]),
+}
+
 
 def lib():
     """Load (once) and return the ctypes handle; raise ExtensionNotLoaded on failure."""
@@ -295,7 +316,8 @@ def lib():
         for name, (res, args) in {**SIGNATURES, **SIGNATURES_STFT_COMPLEX,
                                   **SIGNATURES_SPECTRAL, **SIGNATURES_CSM,
                                   **SIGNATURES_MODES, **SIGNATURES_BISPECTRUM,
-                                  **SIGNATURES_WAVENUMBER, **SIGNATURES_CORRELATION}.items():
+                                  **SIGNATURES_WAVENUMBER, **SIGNATURES_CORRELATION,
+                                  **SIGNATURES_BEAMFORM}.items():
             if dev_build and not hasattr(h, name):
                 continue  # an older revision's build for an A/B run (tools/build_rev_lib.sh)
             fn = getattr(h, name)

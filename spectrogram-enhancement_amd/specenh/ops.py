@@ -848,6 +848,143 @@ _op("herm_eig_out(Tensor a, int k, Tensor(a!)? w, Tensor(b!)? v, Tensor(c!)? swe
     _herm_eig_out, lambda *a: None)
 
 
+# ---------------------------------------------------------------- steered-response spectra
+def _steer_check(V, w, A, post, scale_table):
+    """Rows V[..., M, C] complex64, weights w[..., M] float32 or None, table A[K, C] or
+    [Fa, K, C] complex64 (then V is [..., Fa, G, M, C]); (lead, M, C, K, a_count, a_inner)."""
+    if V.dtype != torch.complex64 or V.dim() < 2:
+        raise ValueError("V must be complex64 [..., M, C]")
+    M, C = V.shape[-2], V.shape[-1]
+    lead = tuple(V.shape[:-2])
+    if M < 1 or not 1 <= C <= _lib.STEER_MAX_CHANNELS:
+        raise ValueError(f"V must hold at least one row of 1 to {_lib.STEER_MAX_CHANNELS} "
+                         f"channels, got [M, C] = [{M}, {C}]")
+    if (A.dtype != torch.complex64 or A.dim() not in (2, 3) or A.shape[-1] != C
+            or not A.is_contiguous() or A.device != V.device):
+        raise ValueError(f"A must be contiguous complex64 [K, {C}] or [F, K, {C}] on V's device")
+    K = A.shape[-2]
+    if not 1 <= K <= _lib.STEER_MAX_NSTEER:
+        raise ValueError(f"K must be in [1, {_lib.STEER_MAX_NSTEER}], got {K}")
+    a_count, a_inner = 1, 1
+    if A.dim() == 3:
+        if len(lead) < 2 or lead[-2] != A.shape[0]:
+            raise ValueError("a table per bin A[F, K, C] needs V[..., F, G, M, C]")
+        a_count, a_inner = A.shape[0], lead[-1]
+    if w is not None and (w.dtype != torch.float32 or tuple(w.shape) != lead + (M,)
+                          or w.device != V.device):
+        raise ValueError(f"w must be float32 {lead + (M,)} on V's device")
+    if scale_table is not None and (scale_table.dtype != torch.float64
+                                    or tuple(scale_table.shape) != (a_count,)
+                                    or scale_table.device != V.device):
+        raise ValueError(f"scale_table must be float64 [{a_count}] on V's device")
+    if not _lib.STEER_SUM <= post <= _lib.STEER_MUSIC:
+        raise ValueError(f"post must be in [0, 3], got {post}")
+    return lead, M, C, K, a_count, a_inner
+
+
+def _steer_layout(V):
+    """(V, count, matrix_stride, row_stride): ``V`` as it is when its rows have unit stride and
+    the leading axes step through memory by one stride that clears a matrix, else its
+    contiguous copy."""
+    M, C = V.shape[-2], V.shape[-1]
+    lead = V.shape[:-2]
+    count = int(np.prod(lead, dtype=np.int64)) if lead else 1
+    rs = V.stride(-2) if M > 1 else C
+    ok = (V.stride(-1) == 1 or C == 1) and rs >= C
+    extent = (M - 1) * rs + C
+    ms = extent
+    dims = [(s, st) for s, st in zip(lead, V.stride()[:-2]) if s != 1]
+    if ok and count > 1 and dims:
+        ms = dims[-1][1]
+        for (_, st0), (s1, st1) in zip(dims[:-1], dims[1:]):
+            ok = ok and st0 == st1 * s1
+        ok = ok and ms >= extent
+    if not ok:
+        V = V.contiguous()
+        ms, rs = M * C, C
+    return V, count, ms, rs
+
+
+def _steered_power_out(V, w, A, post, scale, conj_a, scale_table, out):
+    lead, M, C, K, a_count, a_inner = _steer_check(V, w, A, post, scale_table)
+    if (tuple(out.shape) != lead + (K,) or out.dtype != torch.float32 or not out.is_contiguous()
+            or out.device != V.device):
+        raise ValueError(f"out must be contiguous float32 {lead + (K,)} on V's device")
+    V, count, ms, rs = _steer_layout(V)
+    if count == 0:
+        return
+    if w is not None:
+        w = w.contiguous()
+    _lib.check(_lib.lib().specenh_steered_power(
+        _vp(V), _vp(w), _vp(A), count, M, C, K, ms, rs, a_count, a_inner, int(bool(conj_a)),
+        float(scale), _vp(scale_table), int(post), _vp(out), _st(V)), "steered_power")
+
+
+def _steered_power(V, w, A, post, scale, conj_a, scale_table):
+    lead, _, _, K, _, _ = _steer_check(V, w, A, post, scale_table)
+    out = torch.empty(lead + (K,), dtype=torch.float32, device=V.device)
+    _steered_power_out(V, w, A, post, scale, conj_a, scale_table, out)
+    return out
+
+
+def _steered_power_fake(V, w, A, post, scale, conj_a, scale_table):
+    return V.new_empty(tuple(V.shape[:-2]) + (A.shape[-2],), dtype=torch.float32)
+
+
+_STEER_ARGS = "Tensor V, Tensor? w, Tensor A, int post, float scale, bool conj_a, " \
+              "Tensor? scale_table"
+_op(f"steered_power({_STEER_ARGS}) -> Tensor", _steered_power, _steered_power_fake)
+_op(f"steered_power_out({_STEER_ARGS}, Tensor(a!) out) -> ()", _steered_power_out,
+    lambda *a: None)
+
+
+def _array_spectrum_check(x, nperseg, noverlap, navg, A):
+    if x.dim() != 3 or x.dtype != torch.float32 or x.stride(2) != 1:
+        raise ValueError("x must be float32 [batch, channels, length] with unit stride along "
+                         "length")
+    C, F = x.shape[1], nperseg // 2 + 1
+    if not 1 <= C <= _lib.STEER_MAX_CHANNELS:
+        raise ValueError(f"channels must be in [1, {_lib.STEER_MAX_CHANNELS}], got {C}")
+    if (A.dtype != torch.complex64 or A.dim() not in (2, 3) or A.shape[-1] != C
+            or (A.dim() == 3 and A.shape[0] != F) or not A.is_contiguous()
+            or A.device != x.device):
+        raise ValueError(f"A must be contiguous complex64 [K, {C}] or [{F}, K, {C}] on x's "
+                         "device")
+    K = A.shape[-2]
+    if not 1 <= K <= _lib.STEER_MAX_NSTEER:
+        raise ValueError(f"K must be in [1, {_lib.STEER_MAX_NSTEER}], got {K}")
+    return _avg_check_split(x.shape[2], nperseg, noverlap, navg)[1], K
+
+
+def array_spectrum_workspace(x, nperseg, noverlap, window, fs, scaling, detrend, navg):
+    """A workspace for ``array_spectrum_out`` on ``x[B, C, L]`` (uint8, from torch's caching
+    allocator): the spectra of every frame that enters a group, ``8 B F T C`` bytes."""
+    _, need = _avg_plan(x, (nperseg, noverlap, window, fs, scaling, detrend),
+                        "array_spectrum_workspace_bytes", *x.shape, int(navg))
+    return _avg_buffer(need, x.device)
+
+
+def _array_spectrum_out(x, nperseg, noverlap, window, fs, scaling, detrend, navg, A, out,
+                        workspace):
+    G, K = _array_spectrum_check(x, nperseg, noverlap, navg, A)
+    cs, bs = _csm_strides(x)
+    B, C, L = x.shape
+    shape = (B, nperseg // 2 + 1, G, K)
+    if (tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous()
+            or out.device != x.device):
+        raise ValueError(f"out must be contiguous float32 {shape} on x's device")
+    plan, need = _avg_plan(x, (nperseg, noverlap, window, fs, scaling, detrend),
+                           "array_spectrum_workspace_bytes", B, C, L, int(navg))
+    ws, nbytes = _avg_workspace(workspace, need, x.device)
+    _lib.check(_lib.lib().specenh_array_spectrum(
+        plan.handle, _vp(x), B, C, L, cs, bs, int(navg), _vp(A), K, int(A.dim() == 3), _vp(out),
+        _vp(ws), nbytes, _st(x)), "array_spectrum")
+
+
+_op(f"array_spectrum_out(Tensor x, {_SP_ARGS}, Tensor A, Tensor(a!) out, "
+    "Tensor(b!)? workspace) -> ()", _array_spectrum_out, lambda *a: None)
+
+
 # ---------------------------------------------------------------- SVD denoiser
 def _bstride(A):
     """Batch stride for the C-ABI: a batch of one may carry any stride (e.g. 0 from a numpy

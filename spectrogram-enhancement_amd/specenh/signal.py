@@ -8,7 +8,8 @@ arrays of scipy's shapes. ``welch`` / ``csd`` / ``coherence`` run ``specenh.spec
 fused launch of csrc/spectral_mean.hip; ``average='mean'`` only). ``cross_spectral_matrix``
 (not in scipy) gives ``csd`` / ``coherence`` of every channel pair of an array in one call
 (csrc/spectral_matrix.hip), ``array_modes`` the eigendecomposition of those matrices
-(csrc/herm_eig.hip), ``bicoherence`` (not in scipy) the squared bicoherence of one to three
+(csrc/herm_eig.hip), ``array_spectrum`` (not in scipy) the Bartlett, Capon and MUSIC
+steered-response spectra of an array (csrc/steered_power.hip), ``bicoherence`` (not in scipy) the squared bicoherence of one to three
 signals (csrc/bispectrum.hip), ``wavenumber_spectrum`` (not in scipy) the two-point
 wavenumber-frequency spectrum ``S(k, f)`` of two channels (csrc/wavenumber.hip), ``correlate``
 the block-averaged lagged cross-correlation of two channels (csrc/correlation.hip; per frame
@@ -25,6 +26,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from . import beamform as _beamform
 from . import bispectrum as _bispectrum
 from . import correlation as _correlation
 from . import spectral as _spectral
@@ -221,6 +223,44 @@ def array_modes(x, k=1, fs=1.0, window="hann", nperseg=None, noverlap=None, nfft
         v = v.cpu().numpy().astype(np.complex128 if name == "modes" else np.float64)
         out[name] = v.reshape(lead + v.shape[1:])
     return f, t, out
+
+
+def array_spectrum(x, A, method="bartlett", nsources=1, loading=1e-2, fs=1.0, window="hann",
+                   nperseg=None, noverlap=None, nfft=None, detrend="constant",
+                   return_onesided=True, scaling="density", axis=-1, average="mean", navg=None):
+    """The steered-response spectrum of a channel array ``x[..., C, L]`` on the steering vectors
+    ``A[K, C]`` or ``A[F, K, C]`` (complex; not in scipy): one call of
+    ``specenh.beamform.array_spectrum``, the Bartlett, Capon or MUSIC estimator of every
+    frequency and averaging group (csrc/steered_power.hip). Returns ``(f, t_groups, P)``, ``P``
+    float64 ``[..., F, G, K]``; the leading axes are flattened into the batch and restored."""
+    nperseg = 256 if nperseg is None else int(nperseg)
+    if nfft is not None and int(nfft) != nperseg:
+        raise NotImplementedError("nfft != nperseg is not supported on the GPU path")
+    if not return_onesided:
+        raise NotImplementedError("two-sided spectra are not supported on the GPU path")
+    if average != "mean":
+        if average == "median":
+            raise NotImplementedError("average='median' is not supported on the GPU path")
+        raise ValueError(f"average must be 'median' or 'mean', got {average}")
+    a = np.asarray(x)
+    if np.iscomplexobj(a):
+        raise NotImplementedError("complex input is not supported on the GPU path")
+    if a.ndim < 2:
+        raise ValueError("x must be at least 2-D: [..., channels, length]")
+    if axis not in (-1, a.ndim - 1):
+        raise NotImplementedError("only axis=-1 is supported on the GPU path")
+    if not isinstance(A, torch.Tensor):
+        A = np.asarray(A)
+        if not np.iscomplexobj(A):
+            raise ValueError("A must be complex [K, C] or [F, K, C]")
+        A = torch.from_numpy(np.array(A, dtype=np.complex64, order="C"))
+    xb, lead = _leading(np.array(a, dtype=np.float32, order="C"), 2)
+    f, t, P = _beamform.array_spectrum(
+        _upload(torch.from_numpy(xb)), _upload(A), method=method, nsources=nsources,
+        loading=loading, fs=fs, window=window, nperseg=nperseg, noverlap=noverlap,
+        detrend=detrend, scaling=scaling, navg=navg)
+    P = P.cpu().numpy().astype(np.float64)
+    return f, t, P.reshape(lead + P.shape[1:])
 
 
 def bicoherence(x, y=None, z=None, fs=1.0, window="hann", nperseg=None, noverlap=None,
