@@ -24,6 +24,9 @@ block-averaged lagged cross-correlation (time-delay estimation, correlation time
 steered-response spectra of a channel array (Bartlett, Capon, MUSIC: mode numbers, wavenumbers):
   specenh.signal.array_spectrum (numpy); specenh.beamform.array_spectrum,
   mode_number_spectrum, steered_power, steering_vectors, delay_steering (device tensors)
+continuous wavelet transform (Morlet scalogram) and complex FIR filter bank:
+  specenh.signal.cwt (numpy); specenh.wavelet.cwt, scalogram, filter_bank, FilterBank,
+  morlet_filters, morlet_scales, scale_to_frequency, cone_of_influence (device tensors)
 Device fast paths: specgr_batch, denoise_batch, cross_spectrogram_batch, and
 specenh.autograd (differentiable Conv2D / Conv2DTranspose / MaxPooling2D / BCE).
 Every one of them reaches the HIP kernels through the ``torch.ops.specenh`` operators

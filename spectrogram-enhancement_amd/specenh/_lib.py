@@ -295,6 +295,20 @@ SIGNATURES_BEAMFORM = {
                                           _c.c_size_t, _c.c_void_p]),
 }
 
+# complex FIR filter bank (wavelet transform); must match include/specenh_wavelet.h
+FB_COMPLEX, FB_POWER, FB_POWER_MEAN = 0, 1, 2  # SPECENH_FB_*: what an output element holds
+FB_MAX_HALF = 1024  # SPECENH_FB_MAX_HALF
+FB_NFFT = (256, 512, 1024, 2048, 4096)  # the transform lengths of the overlap-save blocks
+SIGNATURES_WAVELET = {
+    "specenh_filterbank_nfft": (_c.c_int, [_c.c_int, _c.c_int]),
+    "specenh_filterbank_tables_bytes": (_c.c_size_t, [_c.c_int, _c.c_int]),
+    "specenh_filterbank_tables": (_c.c_int, [_c.c_int, _c.POINTER(_c.c_int),
+                                             _c.POINTER(_c.c_double), _c.c_int, _c.c_void_p]),
+    "specenh_filterbank": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p,
+                                      _c.c_longlong, _c.c_longlong, _c.c_longlong,
+                                      _c.c_longlong, _c.c_int, _c.c_void_p, _c.c_void_p]),
+}
+
 
 def lib():
     """Load (once) and return the ctypes handle; raise ExtensionNotLoaded on failure."""
@@ -317,7 +331,7 @@ def lib():
                                   **SIGNATURES_SPECTRAL, **SIGNATURES_CSM,
                                   **SIGNATURES_MODES, **SIGNATURES_BISPECTRUM,
                                   **SIGNATURES_WAVENUMBER, **SIGNATURES_CORRELATION,
-                                  **SIGNATURES_BEAMFORM}.items():
+                                  **SIGNATURES_BEAMFORM, **SIGNATURES_WAVELET}.items():
             if dev_build and not hasattr(h, name):
                 continue  # an older revision's build for an A/B run (tools/build_rev_lib.sh)
             fn = getattr(h, name)

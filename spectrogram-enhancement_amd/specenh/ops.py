@@ -777,6 +777,109 @@ _op(f"correlation_out(Tensor x, Tensor y, {_SP_ARGS}, int maxlag, int normalize,
     lambda *a: None)
 
 
+# ---------------------------------------------------------------- complex FIR filter bank
+_FB_KINDS = (_lib.FB_COMPLEX, _lib.FB_POWER, _lib.FB_POWER_MEAN)
+
+
+def filterbank_nfft(lmax: int, nfft=None) -> int:
+    """The transform length of a bank whose longest filter has the half length ``lmax``:
+    ``nfft`` checked, or (None / 0) the default, the smallest allowed power of two
+    ``>= 4 lmax`` and at least 1024 (specenh_filterbank_nfft)."""
+    return _lib.check(_lib.lib().specenh_filterbank_nfft(int(lmax), int(nfft or 0)),
+                      "filterbank_nfft")
+
+
+def filterbank_tables(taps, half_lengths, nfft, device="cuda") -> torch.Tensor:
+    """The tables of a bank as the operators take them, complex64 ``[S + 1, nfft]`` on
+    ``device``: row ``s`` the DFT of filter ``s`` wrapped circularly, the last row the
+    twiddles (specenh_filterbank_tables: host, fp64, rounded once). ``taps``: the filters one
+    after the other, complex, filter ``s`` as its ``2 L_s + 1`` taps from ``m = -L_s``;
+    ``half_lengths``: the ``L_s``."""
+    hl = np.ascontiguousarray(half_lengths, dtype=np.intc).reshape(-1)
+    h = np.ascontiguousarray(taps, dtype=np.complex128).reshape(-1)
+    S = int(hl.shape[0])
+    if S < 1:
+        raise ValueError("a filter bank needs at least one filter")
+    if (hl < 0).any() or h.shape[0] != int((2 * hl.astype(np.int64) + 1).sum()):
+        raise ValueError("taps must hold 2 L_s + 1 values for every half length L_s >= 0")
+    nfft = int(nfft)
+    L = _lib.lib()
+    need = int(L.specenh_filterbank_tables_bytes(S, nfft))
+    if need == 0:
+        _lib.check(_lib.SPECENH_EINVAL, "filterbank_tables")
+    host = np.empty((S + 1, nfft), dtype=np.complex64)
+    assert host.nbytes == need
+    _lib.check(L.specenh_filterbank_tables(
+        S, hl.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+        h.view(np.float64).ctypes.data_as(ctypes.POINTER(ctypes.c_double)), nfft,
+        ctypes.c_void_p(host.ctypes.data)), "filterbank_tables")
+    return torch.from_numpy(host).to(device)
+
+
+def _fb_check(x, tables, lmax, hop, kind):
+    """(filters, nfft, outputs per filter) of a call; plain arithmetic, on meta tensors too."""
+    if x.dim() != 2 or x.stride(1) != 1 or x.dtype != torch.float32:
+        raise ValueError("x must be float32 [batch, length] with unit stride along length")
+    if (tables.dim() != 2 or tables.dtype != torch.complex64 or tables.shape[0] < 2
+            or not tables.is_contiguous() or tables.device != x.device):
+        raise ValueError("tables must be contiguous complex64 [filters + 1, nfft] on x's device")
+    S, nfft = tables.shape[0] - 1, tables.shape[1]
+    if nfft not in _lib.FB_NFFT:
+        raise ValueError(f"nfft must be one of {_lib.FB_NFFT}, got {nfft}")
+    if not 0 <= lmax <= _lib.FB_MAX_HALF:
+        raise ValueError(f"lmax must be in [0, {_lib.FB_MAX_HALF}], got {lmax}")
+    if hop < 1:
+        raise ValueError(f"hop must be >= 1, got {hop}")
+    if 2 * lmax + hop > nfft:
+        raise ValueError(f"2 lmax + hop must not exceed nfft: 2 * {lmax} + {hop} > {nfft}")
+    if kind not in _FB_KINDS:
+        raise ValueError(f"kind must be {_lib.FB_COMPLEX} (complex), {_lib.FB_POWER} (power) or "
+                         f"{_lib.FB_POWER_MEAN} (mean power)")
+    L = x.shape[1]
+    if L < 1:
+        raise ValueError("length must be >= 1")
+    if kind == _lib.FB_POWER_MEAN:
+        if L < hop:
+            raise ValueError(f"signal of {L} samples is shorter than hop = {hop}")
+        return S, nfft, L // hop
+    return S, nfft, (L - 1) // hop + 1
+
+
+def _fb_dtype(kind):
+    return torch.complex64 if kind == _lib.FB_COMPLEX else torch.float32
+
+
+def _filterbank_out(x, tables, lmax, hop, kind, out):
+    S, nfft, To = _fb_check(x, tables, lmax, hop, kind)
+    B, L = x.shape
+    shape = (B, S, To)
+    if (out.shape != shape or out.dtype != _fb_dtype(kind) or not out.is_contiguous()
+            or out.device != x.device):
+        raise ValueError(f"out must be contiguous {_fb_dtype(kind)} {shape} on x's device")
+    _lib.check(_lib.lib().specenh_filterbank(
+        _vp(tables), S, nfft, int(lmax), _vp(x), B, L, _avg_stride(x), int(hop), int(kind),
+        _vp(out), _st(x)), "filterbank")
+
+
+def _filterbank(x, tables, lmax, hop, kind):
+    S, _, To = _fb_check(x, tables, lmax, hop, kind)
+    out = torch.empty((x.shape[0], S, To), dtype=_fb_dtype(kind), device=x.device)
+    _filterbank_out(x, tables, lmax, hop, kind, out)
+    return out
+
+
+def _filterbank_fake(x, tables, lmax, hop, kind):
+    S, _, To = _fb_check(x, tables, lmax, hop, kind)
+    return x.new_empty((x.shape[0], S, To), dtype=_fb_dtype(kind))
+
+
+# `kind` is the C entry's mode (see the note on `normalize` above)
+_op("filterbank(Tensor x, Tensor tables, int lmax, int hop, int kind) -> Tensor", _filterbank,
+    _filterbank_fake)
+_op("filterbank_out(Tensor x, Tensor tables, int lmax, int hop, int kind, Tensor(a!) out) -> ()",
+    _filterbank_out, lambda *a: None)
+
+
 # ---------------------------------------------------------------- Hermitian eigensolver
 def _eig_check(a, k):
     if a.dtype != torch.complex64 or a.dim() < 2 or a.shape[-1] != a.shape[-2]:

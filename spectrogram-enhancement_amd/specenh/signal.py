@@ -13,7 +13,8 @@ steered-response spectra of an array (csrc/steered_power.hip), ``bicoherence`` (
 signals (csrc/bispectrum.hip), ``wavenumber_spectrum`` (not in scipy) the two-point
 wavenumber-frequency spectrum ``S(k, f)`` of two channels (csrc/wavenumber.hip), ``correlate``
 the block-averaged lagged cross-correlation of two channels (csrc/correlation.hip; per frame
-``scipy.signal.correlate(y_t, x_t)``). There is no CPU fallback.
+``scipy.signal.correlate(y_t, x_t)``), ``cwt`` (no longer in scipy) the Morlet continuous
+wavelet transform (csrc/filterbank.hip). There is no CPU fallback.
 
 Differences from scipy, each one an exception rather than another result:
 ``nfft != nperseg``, two-sided spectra, axes other than the defaults, and the ``'even'``,
@@ -31,7 +32,9 @@ from . import bispectrum as _bispectrum
 from . import correlation as _correlation
 from . import spectral as _spectral
 from . import stft as _stft
+from . import wavelet as _wavelet
 from . import wavenumber as _wavenumber
+from ._lib import FB_MAX_HALF as _FB_MAX_HALF
 
 
 def _upload(t: torch.Tensor) -> torch.Tensor:
@@ -342,3 +345,35 @@ def correlate(x, y, window="boxcar", nperseg=None, noverlap=None, detrend="const
         maxlag=maxlag, normalize=normalize, unbiased=unbiased, fs=fs)
     R = R.cpu().numpy().astype(np.float64)
     return lags, t, R.reshape(lead + R.shape[1:])
+
+
+def cwt(x, fs=1.0, freqs=None, fmin=None, fmax=None, voices_per_octave=16, hop=1, w0=6.0,
+        support=4.0, nfft=None):
+    """The Morlet continuous wavelet transform (one call of ``specenh.wavelet.cwt``,
+    csrc/filterbank.hip; not in scipy since ``scipy.signal.cwt`` was removed): Torrence &
+    Compo's ``W_n(s)`` with ``dt = 1`` at the scales of ``freqs`` (Hz), or, ``freqs`` None, at
+    ``wavelet.morlet_scales(fmin, fmax, fs, voices_per_octave)`` with ``fmin`` defaulting to
+    the lowest frequency whose wavelet has a half length of 1024 samples and ``fmax`` to
+    ``fs / 4``. Returns ``(freqs, t, W)``: ``freqs`` float64 ``[S]``
+    (``wavelet.scale_to_frequency``), ``t = arange(To) * hop / fs`` and ``W`` complex128
+    ``[..., S, To]``; the leading axes are flattened into the batch and restored."""
+    a = np.asarray(x)
+    if np.iscomplexobj(a):
+        raise NotImplementedError("complex input is not supported on the GPU path")
+    if a.ndim == 0:
+        raise ValueError("x must be at least 1-D")
+    if freqs is None:
+        fmax = fs / 4.0 if fmax is None else fmax
+        if fmin is None:
+            fmin = float(_wavelet.scale_to_frequency(_FB_MAX_HALF / support, fs, w0)[0])
+        scales = _wavelet.morlet_scales(fmin, fmax, fs, voices_per_octave, w0)
+        while np.ceil(support * scales[-1]) > _FB_MAX_HALF:  # the step past fmin
+            scales = scales[:-1]
+    else:
+        scales = _wavelet.frequency_to_scale(freqs, fs, w0)
+    flat, lead = _leading(np.array(a, dtype=np.float32, order="C"), 1)
+    W = _wavelet.cwt(_upload(torch.from_numpy(flat)), scales, hop=hop, w0=w0, support=support,
+                     nfft=nfft)
+    W = W.cpu().numpy().astype(np.complex128)
+    t = np.arange(W.shape[-1], dtype=np.float64) * hop / float(fs)
+    return _wavelet.scale_to_frequency(scales, fs, w0), t, W.reshape(lead + W.shape[1:])
