@@ -1,7 +1,9 @@
 """The fp64 restatement of the steered-response spectra (numpy and scipy only): the raw weighted
 sum of squared projections, the Bartlett, Capon and MUSIC estimators from a matrix or from given
 eigenpairs, the cross-spectral matrices of scipy.signal.csd, and the signal generator the
-beamforming tests share (plane-wave modes plus white noise on an irregular angle array).
+beamforming tests share (plane-wave modes plus white noise on an irregular angle array); the
+case grids of the kernel tests, and the two CPU measurements their tolerances come from
+(restatement32_error, chain32).
 
 Conventions (include/specenh_beamform.h): S_ij = mean conj(X_i) X_j, a_c = exp(i kappa p_c),
 a fluctuation X_c ~ exp(i kappa0 p_c) peaks at kappa = kappa0."""
@@ -96,12 +98,44 @@ def kernel_case(M, C, K, count, per_bin):
     return V, A, w
 
 
-# (M, C, K, count, per_bin): every value of each axis at least once, the corners together
+# (M, C, K, count, per_bin): the ends of each axis together (M, C in {1, 64}, K in {1, 257},
+# count in {1, 7}) and the values around one tile of 32 rows, 32 channels and 32 steering rows.
+# Of the channel axis that is C = 1, 2, 3, 31, 32, 33, 63, 64: four of the kernel's eight
+# instantiations (KH = 4, 16, 20, 32). CHANNEL_CASES below visits the rest.
 KERNEL_CASES = [(1, 1, 1, 1, False), (64, 64, 257, 7, False), (1, 64, 257, 1, False),
                 (64, 1, 1, 7, True), (2, 2, 31, 7, False), (15, 3, 32, 1, False),
                 (16, 31, 33, 7, True), (17, 32, 65, 1, False), (31, 33, 257, 7, True),
                 (32, 63, 1, 1, False), (33, 64, 65, 7, True), (64, 3, 31, 7, False),
                 (1, 64, 1, 7, False), (64, 1, 257, 1, False)]
+
+# One case per channel count: launch_steered (csrc/steered_power.hip) picks the instantiation
+# steered_power_kernel<KH> by (C - 1) / 8, KH = 4, 8, .. 32, eight channel counts each, and
+# lane half h owns the channels [h KH, (h + 1) KH): C = 1 (mod 8) leaves the high half one
+# channel, C = 0 (mod 8) none to pad. M gives one to four row tiles with a partial last one, K
+# one wave, a full workgroup and a second one. No M = 1: a single random row makes 1 / q
+# ill-conditioned (the fp32 restatement itself is off by 9.6e-6 there for INVERSE), which would
+# test the conditioning and not the kernel.
+CHANNEL_CASES = [((16, 31, 33, 65, 97)[C % 5], C, (1, 31, 33, 129, 130)[(C // 3) % 5], 3,
+                  bool(C & 1)) for C in range(1, 65)]
+
+
+def instantiation(C):
+    """The index of the kernel launch_steered picks: steered_power_kernel<4 (index + 1)>."""
+    return (C - 1) // 8
+
+
+def restatement32_error(cases):
+    """The error of the fp32 restatement against the fp64 one over `cases`, w null and given:
+    [SUM, BARTLETT, INVERSE, MUSIC] normwise, the epilogue in fp64 on the fp32 sum as in the
+    kernel. The kernel tolerances are 4 x this on KERNEL_CASES."""
+    worst = [0.0] * 4
+    for case in cases:
+        V, A, w = kernel_case(*case)
+        for ww in (None, w):
+            q, q32 = raw_q(V, ww, A), raw_q32(V, ww, A).astype(np.float64)
+            for mode in range(4):
+                worst[mode] = max(worst[mode], normwise(post(q32, A, mode), post(q, A, mode)))
+    return worst
 
 
 def bartlett(S, A):
@@ -203,6 +237,51 @@ def signals(B, C, L, seed=0):
     x = x.astype(np.float32)
     x.setflags(write=False)
     return x
+
+
+# the end-to-end case of Capon and MUSIC: 24 frames of 64 / 48 in three blocks of 8, 5 samples
+# left over, two shots, mode numbers -8 .. 8 on the irregular angles, loading 1e-2, two sources
+N_MODES = np.arange(-8, 9)
+L_E2E = 64 + 16 * 23 + 5
+E2E_KW = dict(fs=FS, window="hann", nperseg=64, noverlap=48, detrend="constant", navg=8)
+E2E_SOURCES, E2E_LOADING = 2, 1e-2
+
+
+@functools.lru_cache(maxsize=None)
+def e2e_reference(C):
+    """(x float32 [2, C, L_E2E], S complex128 [2, 33, 3, C, C] of scipy.signal.csd, A complex64
+    [17, C])."""
+    x = signals(2, C, L_E2E)
+    S = scipy_csm(x, 64, 48, "hann", "constant", 8)
+    S.setflags(write=False)
+    return x, S, steering(angles(C), N_MODES).astype(np.complex64)
+
+
+@functools.lru_cache(maxsize=None)
+def chain32(C):
+    """What an fp32 eigensolver costs Capon and MUSIC on e2e_reference(C): the normwise
+    difference between oracle/herm_eig.py (the fp32 restatement of csrc/herm_eig.hip's method)
+    feeding the fp64 projection, and the all-fp64 chain (numpy.linalg.eigh), both on the scipy
+    matrices. {method: value}: the entries (C, method) of CHAIN32."""
+    from oracle import herm_eig
+
+    _, S, A = e2e_reference(C)
+    lam, v, _ = herm_eig.herm_eig_batch(S.reshape(-1, C, C))
+    lam, v = lam.reshape(S.shape[:-1]), v.reshape(S.shape)
+    return {method: normwise(
+        from_eigenpairs(lam, v, A, method, E2E_SOURCES, E2E_LOADING),
+        estimate(S, A, method, E2E_SOURCES, E2E_LOADING)) for method in ("capon", "music")}
+
+
+# chain32(C)[method], to three digits, as measured on the CPU; the end-to-end bound of Capon
+# and MUSIC against scipy matrices is 8 x this (tests/test_beamform_gpu.py), and
+# tests/test_beamform_cpu.py recomputes every entry
+CHAIN32 = {(5, "capon"): 4.03e-6, (5, "music"): 1.83e-5, (12, "capon"): 1.79e-5,
+           (12, "music"): 1.45e-5, (20, "capon"): 3.04e-5, (20, "music"): 1.27e-5,
+           (40, "capon"): 5.62e-5, (40, "music"): 1.26e-5, (44, "capon"): 5.64e-5,
+           (44, "music"): 1.43e-5, (52, "capon"): 7.23e-5, (52, "music"): 1.02e-5,
+           (64, "capon"): 6.90e-5, (64, "music"): 1.18e-5}
+E2E_CHANNELS = sorted({C for C, _ in CHAIN32})
 
 
 def local_maxima(p):

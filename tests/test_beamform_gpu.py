@@ -12,14 +12,20 @@ covers the order of summation, which differs between numpy and the MFMA chain.
 
 Capon and MUSIC against scipy matrices: the bound is 8 x the normwise difference, measured on
 the CPU on these same signals, between oracle/herm_eig.py (the fp32 restatement of the solver)
-feeding the fp64 projection and the all-fp64 chain: CHAIN32 below (C = 5: Capon 4.03e-6, MUSIC
-1.83e-5; C = 40: 5.62e-5, 1.26e-5; C = 64: 6.90e-5, 1.18e-5; pointwise up to 3.5e-4). The 8 x
-covers the CSM's own 5e-7 and the projection's rounding on top of the eigenpairs'.
+feeding the fp64 projection and the all-fp64 chain: beamform_local.chain32, recorded in
+beamform_local.CHAIN32 and recomputed by tests/test_beamform_cpu.py (Capon / MUSIC at C = 5:
+4.03e-6 / 1.83e-5; 12: 1.79e-5 / 1.45e-5; 20: 3.04e-5 / 1.27e-5; 40: 5.62e-5 / 1.26e-5; 44:
+5.64e-5 / 1.43e-5; 52: 7.23e-5 / 1.02e-5; 64: 6.90e-5 / 1.18e-5; pointwise up to 3.5e-4). The
+8 x covers the CSM's own 5e-7 and the projection's rounding on top of the eigenpairs'.
+
+The channel axis: steered_power_kernel<KH> has eight instantiations picked by (C - 1) / 8;
+beamform_local.CHANNEL_CASES runs the kernel at every C in 1 .. 64 at the same tolerances
+(tests/test_beamform_cpu.py asserts that the fp32 restatement is no worse there), the padding
+channels of an instantiation are compared bit for bit with explicit zeros, and the fused and
+end-to-end tests run at C = 12, 20, 44 and 52 as well (KH = 8, 12, 24, 28).
 
 Every output is NaN-filled before the launch. Each test prints measured against allowed
 (pytest -s)."""
-import functools
-
 import numpy as np
 import pytest
 import scipy.signal
@@ -34,9 +40,8 @@ CPU32_Q, CPU32_INV = 5.12e-7, 9.59e-7
 TOL_Q, TOL_INV = 4 * CPU32_Q, 4 * CPU32_INV
 TOL_POST = (TOL_Q, TOL_Q, TOL_INV, TOL_INV)
 TOL_CSM = 1e-5
-CHAIN32 = {(5, "capon"): 4.03e-6, (5, "music"): 1.83e-5, (40, "capon"): 5.62e-5,
-           (40, "music"): 1.26e-5, (64, "capon"): 6.90e-5, (64, "music"): 1.18e-5}
-N_MODES = np.arange(-8, 9)
+CHAIN32 = bl.CHAIN32
+N_MODES = bl.N_MODES
 NAN = float("nan")
 SCALING = {"density": 0, "spectrum": 1}
 DETREND = {False: 0, "constant": 1, "linear": 2}
@@ -74,9 +79,13 @@ def fused(dev, x, n, nov, window, detrend, navg, A, scaling="density", nan_ws=Tr
     return out.cpu().numpy(), ws
 
 
-@pytest.mark.parametrize("case", bl.KERNEL_CASES, ids=lambda c: "M%d-C%d-K%d-n%d-%s" % (
-    c[:4] + ("perbin" if c[4] else "one",)))
-def test_kernel_against_the_restatement(gpu_device, case):
+def case_id(c):
+    return "M%d-C%d-K%d-n%d-%s" % (c[:4] + ("perbin" if c[4] else "one",))
+
+
+def kernel_against_the_restatement(gpu_device, case):
+    """The four epilogues with w null and given, then conj(A) with a scale and a factor per
+    table, against the fp64 restatement on the same inputs."""
     M, C, K, count, per_bin = case
     V, A, w = bl.kernel_case(*case)
     worst = [0.0] * 4
@@ -97,6 +106,61 @@ def test_kernel_against_the_restatement(gpu_device, case):
     err = bl.normwise(got, ref)
     print(f"[{case}] conj, scaled: {err:.2e} (allowed {TOL_Q:.2e})")
     assert err <= TOL_Q
+
+
+@pytest.mark.parametrize("case", bl.KERNEL_CASES, ids=case_id)
+def test_kernel_against_the_restatement(gpu_device, case):
+    kernel_against_the_restatement(gpu_device, case)
+
+
+@pytest.mark.parametrize("case", bl.CHANNEL_CASES, ids=case_id)
+def test_kernel_at_every_channel_count(gpu_device, case):
+    """Every C in 1 .. 64: all eight instantiations steered_power_kernel<KH>, eight channel
+    counts each, with one to four row tiles and one or two workgroups a matrix, at the
+    tolerances of test_kernel_against_the_restatement."""
+    print(f"[C={case[1]}: KH = {4 * (bl.instantiation(case[1]) + 1)}]")
+    kernel_against_the_restatement(gpu_device, case)
+
+
+PAD_CHANNELS = (9, 12, 17, 20, 25, 41, 44, 49, 52, 57)
+
+
+@pytest.mark.parametrize("C", PAD_CHANNELS)
+def test_padding_channels_are_exact_zeros(gpu_device, C):
+    """The channels between C and the 2 KH an instantiation walks are predicated zero loads:
+    the result equals, bit for bit, that of the same data padded with explicit zeros to
+    8 ceil(C / 8) channels (the same instantiation; a lane's k order depends on KH alone and
+    a zero operand adds +-0). The rows of V are views into a wider buffer whose gaps are NaN,
+    as in test_generic_structure_is_bitwise. The operator takes the table contiguous only (the
+    C ABI has no row stride for it), so A sits in a flat NaN-filled buffer with NaN right before
+    its first and after its last row: a load past a row of V or past the table's end puts NaN
+    into the output, one past an inner row of A changes |a|^2 and so the MUSIC bits."""
+    dev = gpu_device
+    M, K, count = 33, 33, 3  # two row tiles and two waves, the second ones with a single row
+    V, A, w = bl.kernel_case(M, C, K, count, False)
+    Cp = 8 * -(-C // 8)
+    assert Cp > C and bl.instantiation(Cp) == bl.instantiation(C)
+    Vp = np.zeros((count, 1, M, Cp), np.complex64)
+    Vp[..., :C] = V
+    Ap = np.zeros((K, Cp), np.complex64)
+    Ap[:, :C] = A
+    wide = torch.full((count, 1, M + 3, Cp + 5), complex(NAN, NAN), dtype=torch.complex64,
+                      device=dev)
+    wide[:, :, :M, :C] = up(dev, V)
+    view = wide[:, :, :M, :C]
+    assert not view.is_contiguous() and view.stride(-2) > C
+    flat = torch.full((K * C + 2 * Cp,), complex(NAN, NAN), dtype=torch.complex64, device=dev)
+    flat[Cp:Cp + K * C] = up(dev, A).reshape(-1)
+    table = flat[Cp:Cp + K * C].view(K, C)
+    assert table.is_contiguous() and table.data_ptr() % 8 == 0
+    for post in (bl.SUM, bl.MUSIC):
+        got = steer(dev, view, up(dev, w), table, post)
+        assert not np.isnan(got).any(), "a predicated load read past a row"
+        padded = steer(dev, Vp, w, Ap, post)
+        differ = int((got.view(np.uint32) != padded.view(np.uint32)).sum())
+        print(f"[C={C} as {Cp}, post {post}] elements that differ from explicit zeros: {differ} "
+              f"of {got.size}, normwise {bl.normwise(got, padded):.2e} (allowed: none)")
+        assert np.array_equal(got, padded)
 
 
 def test_w_all_ones_is_w_null_bitwise(gpu_device):
@@ -170,6 +234,8 @@ def test_long_reduction(gpu_device):
 FUSED = [(5, 256, 128, "hann", "linear", 2, 17, False),
          (40, 64, 48, "hann", "constant", 0, 65, False),
          (33, 256, 128, "hamm", "constant", 0, 17, True)]
+# the instantiations KH = 8, 12, 24, 28, which no other fused case launches
+FUSED += [(C, 64, 48, "hann", "constant", 0, 65, False) for C in (12, 20, 44, 52)]
 
 
 def table(C, K, F, per_bin, seed=0):
@@ -181,7 +247,7 @@ def table(C, K, F, per_bin, seed=0):
     return np.exp(-2j * np.pi * f[:, None, None] * tau[None]).astype(np.complex64)
 
 
-@pytest.mark.parametrize("cfg", FUSED, ids=["C5", "C40", "C33-perbin"])
+@pytest.mark.parametrize("cfg", FUSED, ids=["C5", "C40", "C33-perbin", "C12", "C20", "C44", "C52"])
 def test_fused_bartlett_end_to_end(gpu_device, cfg):
     from test_csm_gpu import signals
 
@@ -226,22 +292,15 @@ def test_fused_bartlett_edge_lengths(gpu_device, L, navg):
     assert err <= TOL_CSM
 
 
-L_E2E = 64 + 16 * 23 + 5  # 24 frames of 64 / 48: three blocks of 8, 5 samples left over
-E2E_KW = dict(fs=FS, window="hann", nperseg=64, noverlap=48, detrend="constant", navg=8)
+L_E2E = bl.L_E2E  # 24 frames of 64 / 48: three blocks of 8, 5 samples left over
+E2E_KW = bl.E2E_KW
+e2e_reference = bl.e2e_reference
 
 
-@functools.lru_cache(maxsize=None)
-def e2e_reference(C):
-    x = bl.signals(2, C, L_E2E)
-    S = bl.scipy_csm(x, 64, 48, "hann", "constant", 8)
-    S.setflags(write=False)
-    return x, S, bl.steering(bl.angles(C), N_MODES).astype(np.complex64)
-
-
-@pytest.mark.parametrize("C", [5, 40, 64])
+@pytest.mark.parametrize("C", [5, 40, 64, 12, 20, 44, 52])
 def test_capon_and_music_end_to_end(gpu_device, C):
-    """Blocks of 8 frames (< C for 40 and 64 channels: rank-deficient matrices), loading 1e-2,
-    two sources."""
+    """Blocks of 8 frames (< C from 12 channels up: rank-deficient matrices), loading 1e-2,
+    two sources. C = 12, 20, 44, 52: the instantiations KH = 8, 12, 24, 28."""
     from specenh import beamform, spectral
 
     x, S, A = e2e_reference(C)

@@ -377,6 +377,74 @@ def test_sign_convention_of_the_restatement():
     assert np.abs(W - wl.filter_bank_direct(x, [np.conj(h)])[0, 0]).max() > 0.1
 
 
+def test_filters_per_workgroup_restates_the_host_rule():
+    """wl.filters_per_workgroup against the text of specenh_filterbank (the kernel gives no way
+    to observe SC), its values at the MI355X's 256 CUs, and every chunk size reachable with the
+    bank of test_filters_per_workgroup_do_not_change_a_bit at any CU count a device may have."""
+    src = open(os.path.join(REPO, "spectrogram-enhancement_amd", "csrc", "filterbank.hip")).read()
+    src = " ".join(src.split())
+    for line in ("constexpr int MAX_SC = 16;", "constexpr int MIN_SC = 4;",
+                 "a.Vh = (nfft - 2 * lmax) / (int)hop;",
+                 "a.To = mode == SPECENH_FB_POWER_MEAN ? length / hop : (length - 1) / hop + 1;",
+                 "const long long nblk = (a.To + a.Vh - 1) / a.Vh;",
+                 "const long long want = 2LL * device_cus();",
+                 "const long long nb0 = batch < 65535 ? batch : 65535;",
+                 "a.SC = MAX_SC; while (a.SC > MIN_SC && nblk * ((nscales + a.SC - 1) / a.SC) "
+                 "* nb0 < want) a.SC /= 2;"):
+        assert line in src, line
+    cfg = wl.CHUNK_CFG
+    assert (cfg["nfft"], cfg["lmax"], cfg["length"], cfg["S"]) == (256, 32, 401, 33)
+
+    def sc(hop, mode, B, cus):
+        return wl.filters_per_workgroup(256, 32, hop, mode, 401, 33, B, cus)
+
+    # hop 1 at 256 CUs: 3 blocks x 3, 5 or 9 chunks x B against 512
+    assert wl.chunk_batches(1, wl.COMPLEX, 256) == (57, 35, 2)
+    assert [sc(1, wl.COMPLEX, B, 256) for B in (1, 2, 34, 35, 56, 57, 65535, 70000)] == \
+        [4, 4, 4, 8, 8, 16, 16, 16]
+    assert wl.chunk_batches(5, wl.POWER, 256) == (57, 35, 2)
+    assert wl.chunk_batches(37, wl.MEAN, 256) == (86, 52, 2)  # To = 10: two blocks of 5
+    for cus in (32, 64, 104, 110, 120, 228, 256, 304):
+        for hop, mode in wl.CHUNK_CASES:
+            B16, B8, B4 = wl.chunk_batches(hop, mode, cus)
+            assert B4 < B8 < B16
+            assert [sc(hop, mode, B, cus) for B in (B16, B16 - 1, B8, B8 - 1, B4)] == \
+                [16, 8, 8, 4, 4]
+            esize = 8 if mode == wl.COMPLEX else 4
+            assert B16 * 33 * wl.n_out(401, hop, mode) * esize < 10e6  # the largest output
+    # the largest launch of the benchmark shape (128 scales, one 65,536-sample shot, hop 128)
+    assert wl.filters_per_workgroup(4096, 1024, 128, wl.MEAN, 65536, 128, 1, 256) == 8
+    assert wl.filters_per_workgroup(4096, 1024, 128, wl.MEAN, 65536, 128, 64, 256) == 16
+
+
+@pytest.mark.parametrize("hop,mode", wl.CHUNK_CASES)
+def test_float32_restatement_of_the_chunk_bank_meets_a_quarter_of_the_bound(hop, mode):
+    """The precondition of the comparison test_filters_per_workgroup_do_not_change_a_bit makes
+    with the direct sum: rows 0, 1 and the last of the 256-CU batch."""
+    B16 = wl.chunk_batches(hop, mode, 256)[0]
+    x, taps = wl.chunk_signal(B16)[[0, 1, B16 - 1]], wl.chunk_taps()
+    f32 = wl.filter_bank_fft32(x, taps, wl.CHUNK_CFG["nfft"], wl.CHUNK_CFG["lmax"], hop, mode)
+    err = wl.compare(f32, wl.filter_bank_direct(x, taps, hop, mode), mode)
+    print(f"\n[chunk bank float32 restatement, hop {hop} mode {mode}] {err:.2e} "
+          f"(bound {wl.bound(mode) / 4:.1e})")
+    assert err <= wl.bound(mode) / 4
+
+
+def test_hop_configurations_cover_both_mean_paths_at_every_nfft():
+    for nfft in wl.NFFTS:
+        name = f"hop{nfft}"
+        n, lmax, spec, length, B, kind = wl.CONFIGS[name]
+        V1 = nfft - 2 * lmax
+        assert (n, lmax, length, B, kind) == (nfft, nfft // 8, 2 * V1 + 17, 2, "white")
+        assert len(wl.taps_of(name)) == 5 and max(h.size // 2 for h in wl.taps_of(name)) == lmax
+        assert wl.hops_of(name) == (1, 16, 17, 37, V1)
+        runs = [-(-h // 16) for h in wl.hops_of(name)]   # P of csrc/filterbank.hip
+        assert runs == [1, 1, 2, 3, V1 // 16] and V1 % 16 == 0
+        assert wl.block_len(nfft, lmax, 37) < V1 and 37 % 16   # V rounds down, a partial run
+        assert len(wl.cases(name)) == 15
+    assert wl.CONFIGS["hop4096"][3] == 6161
+
+
 @pytest.mark.parametrize("name", list(wl.CONFIGS))
 def test_float32_overlap_save_restatement_meets_a_quarter_of_the_bound(name):
     """The precondition of tests/test_wavelet_gpu.py: the overlap-save formulation in float32

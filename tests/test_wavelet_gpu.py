@@ -56,7 +56,9 @@ def test_parity_with_the_fp64_restatement(gpu_device, name):
     """Every nfft at its largest Lmax and with a single tap, lengths around the block seams
     (every output compared: the first and last Lmax test the zero extension), hops 1, 3, 7, 37
     and V under both To rules, filter counts 1, 5, 33 of mixed lengths, random non-Hermitian
-    and Morlet taps, in all three modes."""
+    and Morlet taps, in all three modes; and at every nfft the hops 1, 16, 17, 37 and V
+    (hop{nfft}: the hop mean in one run and in two levels, whose partial sums go to the
+    buffer the transform's pass count leaves free)."""
     dev = gpu_device
     bank = bank_of(dev, name)
     x = strided(dev, wl.signal_of(name))
@@ -109,6 +111,51 @@ def test_splitting_the_bank_does_not_change_a_bit(gpu_device, mode):
     hi = launch(x, wv.FilterBank(taps[16:], nfft=nfft, device=dev, lmax=lmax), hop, mode)
     assert lo.shape[1] == 16 and hi.shape[1] == 17
     assert torch.equal(whole, torch.cat([lo, hi], dim=1))
+
+
+@pytest.mark.parametrize("hop,mode", wl.CHUNK_CASES)
+def test_filters_per_workgroup_do_not_change_a_bit(gpu_device, hop, mode):
+    """The filter loop at 16, 8 and 4 filters a workgroup (SC): 33 filters, three chunks of 16
+    with a single filter in the last. The kernel gives no way to observe SC, so the test rests
+    on wavelet_local.filters_per_workgroup, the restatement of the rule in specenh_filterbank
+    (csrc/filterbank.hip) that tests/test_wavelet_cpu.py holds against the host code's text:
+    with the device's CU count it gives the smallest batch B16 that keeps SC = 16, a batch B8
+    that runs at SC = 8, and two shots at SC = 4. The first B8 and the first two shots run
+    alone equal the rows of the B16 run bit for bit, and rows 0, 1 and the last of the B16 run
+    are compared with the float64 direct sum: a loop of 16 filters, each with the next table
+    row loaded under its transform, against a reference and not only against itself."""
+    from specenh import wavelet as wv
+
+    dev = gpu_device
+    cfg = wl.CHUNK_CFG
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    B16, B8, B4 = wl.chunk_batches(hop, mode, cus)
+
+    def sc(B):
+        return wl.filters_per_workgroup(cfg["nfft"], cfg["lmax"], hop, mode, cfg["length"],
+                                        cfg["S"], B, cus)
+
+    assert (sc(B16), sc(B8), sc(B4)) == (16, 8, 4) and B4 < B8 < B16
+    taps = wl.chunk_taps()
+    bank = wv.FilterBank(taps, nfft=cfg["nfft"], device=dev, lmax=cfg["lmax"])
+    assert (bank.nfft, bank.lmax, bank.nscales) == (256, 32, 33)
+    x = wl.chunk_signal(B16)
+    xd = strided(dev, x)
+    full = launch(xd, bank, hop, mode)
+    assert full.numel() * full.element_size() < 10e6
+    for B, chunk in ((B8, 8), (B4, 4)):
+        part = launch(xd[:B], bank, hop, mode)
+        same = torch.equal(part, full[:B])
+        print(f"\n[filters per workgroup, hop {hop} mode {mode}, {cus} CUs] {B} shots at SC = "
+              f"{chunk} against {B16} shots at SC = 16: "
+              f"{'bit-identical' if same else 'DIFFERENT'} (allowed: bit-identical)")
+        assert same, (B, chunk)
+    rows = [0, 1, B16 - 1]
+    ref = wl.filter_bank_direct(x[rows], taps, hop, mode)
+    err = wl.compare(full[rows].cpu().numpy(), ref, mode)
+    print(f"[filters per workgroup, hop {hop} mode {mode}] SC = 16, rows {rows}: max row error "
+          f"/ row max {err:.2e} (bound {wl.bound(mode):.0e})")
+    assert err <= wl.bound(mode)
 
 
 @pytest.mark.parametrize("hop,mode", ((1, wl.COMPLEX), (2, wl.POWER)))

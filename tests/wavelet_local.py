@@ -50,6 +50,21 @@ def n_out(length, hop, mode):
     return length // hop if mode == MEAN else (length - 1) // hop + 1
 
 
+def filters_per_workgroup(nfft, lmax, hop, mode, length, S, B, cus):
+    """SC, the filters a workgroup of filterbank_kernel loops over. The kernel gives no way to
+    observe it, so this restates the rule of the host code, specenh_filterbank in
+    csrc/filterbank.hip (a.Vh, a.To, nblk, then the `while (a.SC > MIN_SC && ...)` loop): 16,
+    halved down to 4 while the launch has fewer than two workgroups a CU. `cus` is the
+    device's compute-unit count (runtime.hpp's device_cus)."""
+    Vh = (nfft - 2 * lmax) // hop
+    To = n_out(length, hop, mode)
+    nblk = (To + Vh - 1) // Vh
+    sc = 16
+    while sc > 4 and nblk * ((S + sc - 1) // sc) * min(B, 65535) < 2 * cus:
+        sc //= 2
+    return sc
+
+
 # ---------------------------------------------------------------- filters and inputs
 def morlet(scales, w0=6.0, support=4.0):
     """The Morlet taps written out independently of specenh.wavelet.morlet_filters."""
@@ -211,12 +226,57 @@ def _configs():
     # Morlet w0 = 6, support 4, 12 scales
     for nfft, lm, kind in ((256, 32, "chirp"), (1024, 256, "dc50"), (4096, 1024, "chirp")):
         c[f"morlet{nfft}-{kind}"] = (nfft, lm, ("morlet", lm), 2 * block_len(nfft, lm) + 17, 1, kind)
+    # the hop paths at every nfft (the buffer that holds a transform's result depends on its
+    # pass count, and the two-level hop mean moves the product to the other one): Lmax =
+    # nfft / 8, five filters of mixed lengths
+    for nfft in NFFTS:
+        lm = nfft // 8
+        c[f"hop{nfft}"] = (nfft, lm, ("random", tuple(mixed_lengths(5, lm)), 21),
+                           2 * block_len(nfft, lm) + 17, 2, "white")
     return c
 
 
 CONFIGS = _configs()
 HOPS_CFG = "S5"                   # the configuration the hop cases run on: nfft 1024, Lmax 256
 HOPS = (1, 3, 7, 37, 512)         # 37: three runs of the hop mean, the last partial; 512 = V
+
+
+def hops_of(name):
+    """The hops a configuration is compared at. hop{nfft}, with V1 = nfft - 2 Lmax: 16 is the
+    last hop whose mean is one run (P = 1), 17 two runs with a single value in the second, 37
+    rounds V down and leaves the last run partial, V1 is one output a block from V1 / 16 runs."""
+    if name == HOPS_CFG:
+        return HOPS
+    if name.startswith("hop"):
+        nfft, lmax = CONFIGS[name][:2]
+        return (1, 16, 17, 37, block_len(nfft, lmax))
+    return (1,)
+
+
+# the bank test_filters_per_workgroup_do_not_change_a_bit runs: 33 filters, three chunks of 16
+CHUNK_CFG = dict(nfft=256, lmax=32, length=401, S=33)
+CHUNK_CASES = ((1, COMPLEX), (5, POWER), (37, MEAN))
+
+
+def chunk_taps():
+    return random_bank(mixed_lengths(CHUNK_CFG["S"], CHUNK_CFG["lmax"]), seed=33)
+
+
+def chunk_signal(B):
+    return signal("white", B, CHUNK_CFG["length"], seed=57)
+
+
+def chunk_batches(hop, mode, cus):
+    """(B16, B8, 2): the smallest batch that keeps SC = 16 on a device of `cus` compute units
+    with the bank of CHUNK_CFG, the smallest that gives SC = 8, and 2 shots (SC = 4), by
+    filters_per_workgroup."""
+    def sc(B):
+        return filters_per_workgroup(CHUNK_CFG["nfft"], CHUNK_CFG["lmax"], hop, mode,
+                                     CHUNK_CFG["length"], CHUNK_CFG["S"], B, cus)
+
+    B16 = next(B for B in range(1, 65536) if sc(B) == 16)
+    B8 = next(B for B in range(1, B16) if sc(B) == 8)
+    return B16, B8, 2
 SEAM_LENGTHS = {256: (1, 191, 192, 193, 401), 4096: (1, 2047, 2048, 2049, 4113)}
 
 
@@ -247,5 +307,5 @@ def reference(name):
 def cases(name):
     """(hop, mode) pairs a configuration is compared at."""
     length = CONFIGS[name][3]
-    hops = HOPS if name == HOPS_CFG else (1,)
-    return [(h, m) for h in hops for m in (COMPLEX, POWER, MEAN) if not (m == MEAN and length < h)]
+    return [(h, m) for h in hops_of(name) for m in (COMPLEX, POWER, MEAN)
+            if not (m == MEAN and length < h)]
