@@ -27,6 +27,9 @@ steered-response spectra of a channel array (Bartlett, Capon, MUSIC: mode number
 continuous wavelet transform (Morlet scalogram) and complex FIR filter bank:
   specenh.signal.cwt (numpy); specenh.wavelet.cwt, scalogram, filter_bank, FilterBank,
   morlet_filters, morlet_scales, scale_to_frequency, cone_of_influence (device tensors)
+cross-wavelet spectrum, wavelet coherence and phase of channel pairs (mode numbers of chirps):
+  specenh.signal.wavelet_coherence (numpy); specenh.wavelet.cross_wavelet, cross_filter_bank,
+  wavelet_coherence, smoothing_windows (device tensors)
 Device fast paths: specgr_batch, denoise_batch, cross_spectrogram_batch, and
 specenh.autograd (differentiable Conv2D / Conv2DTranspose / MaxPooling2D / BCE).
 Every one of them reaches the HIP kernels through the ``torch.ops.specenh`` operators

@@ -309,6 +309,19 @@ SIGNATURES_WAVELET = {
                                       _c.c_longlong, _c.c_int, _c.c_void_p, _c.c_void_p]),
 }
 
+# cross spectrum of a pair through a filter bank; must match include/specenh_wavelet_cross.h
+XWT_POINT, XWT_MEAN = 0, 1  # SPECENH_XWT_*: values at every hop-th sample, or hop-window means
+SIGNATURES_WAVELET_CROSS = {
+    "specenh_filterbank_cross": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int,
+                                            _c.c_void_p, _c.c_void_p, _c.c_longlong,
+                                            _c.c_longlong, _c.c_longlong, _c.c_longlong,
+                                            _c.c_longlong, _c.c_int, _c.c_void_p, _c.c_void_p,
+                                            _c.c_void_p, _c.c_void_p]),
+    "specenh_filterbank_cross_chunk": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_longlong,
+                                                  _c.c_longlong, _c.c_longlong, _c.c_int,
+                                                  _c.c_int]),
+}
+
 
 def lib():
     """Load (once) and return the ctypes handle; raise ExtensionNotLoaded on failure."""
@@ -331,7 +344,8 @@ def lib():
                                   **SIGNATURES_SPECTRAL, **SIGNATURES_CSM,
                                   **SIGNATURES_MODES, **SIGNATURES_BISPECTRUM,
                                   **SIGNATURES_WAVENUMBER, **SIGNATURES_CORRELATION,
-                                  **SIGNATURES_BEAMFORM, **SIGNATURES_WAVELET}.items():
+                                  **SIGNATURES_BEAMFORM, **SIGNATURES_WAVELET,
+                                  **SIGNATURES_WAVELET_CROSS}.items():
             if dev_build and not hasattr(h, name):
                 continue  # an older revision's build for an A/B run (tools/build_rev_lib.sh)
             fn = getattr(h, name)

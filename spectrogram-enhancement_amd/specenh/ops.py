@@ -880,6 +880,68 @@ _op("filterbank_out(Tensor x, Tensor tables, int lmax, int hop, int kind, Tensor
     _filterbank_out, lambda *a: None)
 
 
+# ---------------------------------------------------------------- cross spectrum of a pair
+def _fbx_check(x, y, tables, lmax, hop, kind):
+    """(filters, nfft, outputs per filter) of a call; plain arithmetic, on meta tensors too."""
+    if kind not in (_lib.XWT_POINT, _lib.XWT_MEAN):
+        raise ValueError(f"kind must be {_lib.XWT_POINT} (every hop-th sample) or "
+                         f"{_lib.XWT_MEAN} (hop-window means)")
+    if (y.dim() != 2 or y.stride(1) != 1 or y.dtype != torch.float32 or y.shape != x.shape
+            or y.device != x.device):
+        raise ValueError("y must be float32 [batch, length] like x, on x's device, with unit "
+                         "stride along length")
+    return _fb_check(x, tables, lmax, hop,
+                     _lib.FB_POWER_MEAN if kind == _lib.XWT_MEAN else _lib.FB_POWER)
+
+
+def filterbank_cross_chunk(nscales, nfft, lmax, batch, length, hop, kind, cus=0) -> int:
+    """The filters a workgroup of the cross kernel loops over for this launch on a device of
+    ``cus`` compute units (0: the current device); host arithmetic
+    (specenh_filterbank_cross_chunk). The outputs do not depend on it."""
+    return _lib.check(_lib.lib().specenh_filterbank_cross_chunk(
+        int(nscales), int(nfft), int(lmax), int(batch), int(length), int(hop), int(kind),
+        int(cus)), "filterbank_cross_chunk")
+
+
+def _filterbank_cross_out(x, y, tables, lmax, hop, kind, sxy, sxx, syy):
+    S, nfft, To = _fbx_check(x, y, tables, lmax, hop, kind)
+    B, L = x.shape
+    shape = (B, S, To)
+    if (sxx is None) != (syy is None):
+        raise ValueError("sxx and syy must be both given or both None")
+    for t, name, dt in ((sxy, "sxy", torch.complex64), (sxx, "sxx", torch.float32),
+                        (syy, "syy", torch.float32)):
+        if t is not None and (t.shape != shape or t.dtype != dt or not t.is_contiguous()
+                              or t.device != x.device):
+            raise ValueError(f"{name} must be contiguous {dt} {shape} on x's device")
+    _lib.check(_lib.lib().specenh_filterbank_cross(
+        _vp(tables), S, nfft, int(lmax), _vp(x), _vp(y), B, L, _avg_stride(x), _avg_stride(y),
+        int(hop), int(kind), _vp(sxy), _vp(sxx), _vp(syy), _st(x)), "filterbank_cross")
+
+
+def _filterbank_cross(x, y, tables, lmax, hop, kind):
+    S, _, To = _fbx_check(x, y, tables, lmax, hop, kind)
+    shape = (x.shape[0], S, To)
+    sxy = torch.empty(shape, dtype=torch.complex64, device=x.device)
+    sxx = torch.empty(shape, dtype=torch.float32, device=x.device)
+    syy = torch.empty(shape, dtype=torch.float32, device=x.device)
+    _filterbank_cross_out(x, y, tables, lmax, hop, kind, sxy, sxx, syy)
+    return sxy, sxx, syy
+
+
+def _filterbank_cross_fake(x, y, tables, lmax, hop, kind):
+    S, _, To = _fbx_check(x, y, tables, lmax, hop, kind)
+    shape = (x.shape[0], S, To)
+    return (x.new_empty(shape, dtype=torch.complex64), x.new_empty(shape), x.new_empty(shape))
+
+
+_op("filterbank_cross(Tensor x, Tensor y, Tensor tables, int lmax, int hop, int kind) -> "
+    "(Tensor, Tensor, Tensor)", _filterbank_cross, _filterbank_cross_fake)
+_op("filterbank_cross_out(Tensor x, Tensor y, Tensor tables, int lmax, int hop, int kind, "
+    "Tensor(a!) sxy, Tensor(b!)? sxx, Tensor(c!)? syy) -> ()", _filterbank_cross_out,
+    lambda *a: None)
+
+
 # ---------------------------------------------------------------- Hermitian eigensolver
 def _eig_check(a, k):
     if a.dtype != torch.complex64 or a.dim() < 2 or a.shape[-1] != a.shape[-2]:

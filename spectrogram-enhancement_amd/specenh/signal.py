@@ -14,7 +14,8 @@ signals (csrc/bispectrum.hip), ``wavenumber_spectrum`` (not in scipy) the two-po
 wavenumber-frequency spectrum ``S(k, f)`` of two channels (csrc/wavenumber.hip), ``correlate``
 the block-averaged lagged cross-correlation of two channels (csrc/correlation.hip; per frame
 ``scipy.signal.correlate(y_t, x_t)``), ``cwt`` (no longer in scipy) the Morlet continuous
-wavelet transform (csrc/filterbank.hip). There is no CPU fallback.
+wavelet transform (csrc/filterbank.hip), ``wavelet_coherence`` (not in scipy) the wavelet
+coherence and phase of two channels (csrc/filterbank_cross.hip). There is no CPU fallback.
 
 Differences from scipy, each one an exception rather than another result:
 ``nfft != nperseg``, two-sided spectra, axes other than the defaults, and the ``'even'``,
@@ -347,6 +348,19 @@ def correlate(x, y, window="boxcar", nperseg=None, noverlap=None, detrend="const
     return lags, t, R.reshape(lead + R.shape[1:])
 
 
+def _cwt_scales(fs, freqs, fmin, fmax, voices_per_octave, w0, support):
+    """The Morlet scales (samples) of ``freqs``, or the default geometric ladder of ``cwt``."""
+    if freqs is not None:
+        return _wavelet.frequency_to_scale(freqs, fs, w0)
+    fmax = fs / 4.0 if fmax is None else fmax
+    if fmin is None:
+        fmin = float(_wavelet.scale_to_frequency(_FB_MAX_HALF / support, fs, w0)[0])
+    scales = _wavelet.morlet_scales(fmin, fmax, fs, voices_per_octave, w0)
+    while np.ceil(support * scales[-1]) > _FB_MAX_HALF:  # the step past fmin
+        scales = scales[:-1]
+    return scales
+
+
 def cwt(x, fs=1.0, freqs=None, fmin=None, fmax=None, voices_per_octave=16, hop=1, w0=6.0,
         support=4.0, nfft=None):
     """The Morlet continuous wavelet transform (one call of ``specenh.wavelet.cwt``,
@@ -362,18 +376,35 @@ def cwt(x, fs=1.0, freqs=None, fmin=None, fmax=None, voices_per_octave=16, hop=1
         raise NotImplementedError("complex input is not supported on the GPU path")
     if a.ndim == 0:
         raise ValueError("x must be at least 1-D")
-    if freqs is None:
-        fmax = fs / 4.0 if fmax is None else fmax
-        if fmin is None:
-            fmin = float(_wavelet.scale_to_frequency(_FB_MAX_HALF / support, fs, w0)[0])
-        scales = _wavelet.morlet_scales(fmin, fmax, fs, voices_per_octave, w0)
-        while np.ceil(support * scales[-1]) > _FB_MAX_HALF:  # the step past fmin
-            scales = scales[:-1]
-    else:
-        scales = _wavelet.frequency_to_scale(freqs, fs, w0)
+    scales = _cwt_scales(fs, freqs, fmin, fmax, voices_per_octave, w0, support)
     flat, lead = _leading(np.array(a, dtype=np.float32, order="C"), 1)
     W = _wavelet.cwt(_upload(torch.from_numpy(flat)), scales, hop=hop, w0=w0, support=support,
                      nfft=nfft)
     W = W.cpu().numpy().astype(np.complex128)
     t = np.arange(W.shape[-1], dtype=np.float64) * hop / float(fs)
     return _wavelet.scale_to_frequency(scales, fs, w0), t, W.reshape(lead + W.shape[1:])
+
+
+def wavelet_coherence(x, y, fs=1.0, freqs=None, fmin=None, fmax=None, voices_per_octave=16,
+                      hop=1, smooth=None, w0=6.0, support=4.0, nfft=None):
+    """Wavelet coherence and phase of two channels (one call of
+    ``specenh.wavelet.wavelet_coherence``, csrc/filterbank_cross.hip; not in scipy), at the
+    scales ``cwt`` would use for the same ``freqs`` / ``fmin`` / ``fmax`` /
+    ``voices_per_octave``. Returns ``(freqs, t, coh, phase)``: ``freqs`` float64 ``[S]``,
+    ``t = (arange(To) + 0.5) * hop / fs`` the centres of the ``To = length // hop`` windows,
+    ``coh`` in [0, 1] and ``phase = angle(conj(Wx) Wy)`` float64 ``[..., S, To]`` (negative
+    where ``y`` lags ``x``). ``x`` and ``y`` broadcast on their leading axes; ``smooth`` as in
+    ``specenh.wavelet.wavelet_coherence``."""
+    a, b = np.asarray(x), np.asarray(y)
+    if np.iscomplexobj(a) or np.iscomplexobj(b):
+        raise NotImplementedError("complex input is not supported on the GPU path")
+    if a.ndim == 0 or b.ndim == 0:
+        raise ValueError("x and y must be at least 1-D")
+    scales = _cwt_scales(fs, freqs, fmin, fmax, voices_per_octave, w0, support)
+    tx = _upload(torch.from_numpy(np.array(a, dtype=np.float32, order="C")))
+    ty = tx if y is x else _upload(torch.from_numpy(np.array(b, dtype=np.float32, order="C")))
+    coh, phase, _ = _wavelet.wavelet_coherence(tx, ty, scales, hop=hop, smooth=smooth, w0=w0,
+                                               support=support, nfft=nfft)
+    t = (np.arange(coh.shape[-1], dtype=np.float64) + 0.5) * hop / float(fs)
+    return (_wavelet.scale_to_frequency(scales, fs, w0), t,
+            coh.cpu().numpy().astype(np.float64), phase.cpu().numpy().astype(np.float64))

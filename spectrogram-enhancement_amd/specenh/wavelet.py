@@ -26,6 +26,13 @@ One fused pass (csrc/filterbank.hip through ``torch.ops.specenh.filterbank`` ->
 chip and multiplied with every filter's table there; the products and inverse transforms never
 reach memory. Results stay on the device; scales, frequencies and times are float64 numpy
 arrays computed on the host. The longest filter has ``L <= 1024``; there is no CPU fallback.
+
+Two channels: ``cross_filter_bank`` / ``cross_wavelet`` give ``conj(Wx) Wy``, ``|Wx|^2`` and
+``|Wy|^2`` per scale, sampled or as hop-window means, in one fused pass of their own
+(csrc/filterbank_cross.hip through ``torch.ops.specenh.filterbank_cross``: neither ``Wx`` nor
+``Wy`` is written), and ``wavelet_coherence`` the time-resolved coherence and phase per scale
+(Torrence & Webster 1999; Grinsted et al. 2004): whether a chirp on one probe is coherent with
+the one on another, and with what phase (phase over probe separation is the mode number).
 """
 from __future__ import annotations
 
@@ -196,3 +203,129 @@ def scalogram(x: torch.Tensor, scales, hop: int = 1, mean: bool = True, w0: floa
         _gpu_only(x, "wavelet")
     return filter_bank(x, _morlet_bank(scales, x, w0, support, nfft, bank), hop,
                        "mean_power" if mean else "power")
+
+
+# ---------------------------------------------------------------- two channels
+def cross_filter_bank(x: torch.Tensor, y: torch.Tensor, bank: FilterBank, hop: int = 1,
+                      mean: bool = True):
+    """The cross spectrum of ``x[..., length]`` and ``y[..., length]`` through ``bank`` on a ROCm
+    device, in one fused pass (csrc/filterbank_cross.hip; ``Wx`` and ``Wy`` never reach memory):
+    ``(Sxy, Sxx, Syy)``, complex64 ``conj(Wx) Wy`` and float32 ``|Wx|^2``, ``|Wy|^2``, each
+    ``[..., S, To]``; the means over each whole window of ``hop`` samples (``mean=True``,
+    ``To = length // hop``) or the values at every ``hop``-th sample
+    (``To = (length - 1) // hop + 1``). The leading dimensions of ``x`` and ``y`` broadcast
+    against each other. ``conj(x) y`` as in ``specenh.spectral.csd``: a ``y`` that lags ``x``
+    has a negative phase at the scales that carry the signal."""
+    if not isinstance(x, torch.Tensor) or not isinstance(y, torch.Tensor):
+        raise TypeError("x and y must be torch.Tensors")
+    if not isinstance(bank, FilterBank):
+        raise TypeError("bank must be a FilterBank")
+    if x.dim() < 1 or y.dim() < 1 or x.shape[-1] != y.shape[-1]:
+        raise ValueError("x and y must be [..., length] with the same length")
+    if int(hop) != hop or hop < 1:
+        raise ValueError(f"hop must be a positive integer, got {hop}")
+    if 2 * bank.lmax + hop > bank.nfft:
+        raise ValueError(f"2 lmax + hop must not exceed nfft: 2 * {bank.lmax} + {hop} > "
+                         f"{bank.nfft}")
+    L = x.shape[-1]
+    if L < 1 or (mean and L < hop):
+        raise ValueError(f"signal of {L} samples is shorter than " +
+                         (f"hop = {hop}" if L else "one sample"))
+    try:
+        lead = torch.broadcast_shapes(x.shape[:-1], y.shape[:-1])
+    except RuntimeError:
+        raise ValueError(f"the leading dimensions of x {tuple(x.shape[:-1])} and y "
+                         f"{tuple(y.shape[:-1])} do not broadcast") from None
+    _gpu_only(x, "wavelet")
+    _gpu_only(y, "wavelet")
+    if x.device != bank.device or y.device != bank.device:
+        raise ValueError(f"x is on {x.device}, y on {y.device}, the bank on {bank.device}")
+
+    def rows(v):
+        v = v.expand(lead + (L,)).reshape(-1, L)
+        if v.dtype != torch.float32:
+            v = v.float()
+        if v.stride(1) != 1 or (v.shape[0] > 1 and v.stride(0) < L):
+            v = v.contiguous()  # a broadcast signal (stride 0) is materialised
+        return v
+
+    out = torch.ops.specenh.filterbank_cross(rows(x), rows(y), bank.tables, bank.lmax, int(hop),
+                                             _lib.XWT_MEAN if mean else _lib.XWT_POINT)
+    return tuple(o.reshape(lead + o.shape[1:]) for o in out)
+
+
+def cross_wavelet(x: torch.Tensor, y: torch.Tensor, scales, hop: int = 1, mean: bool = True,
+                  w0: float = W0, support: float = SUPPORT, nfft=None,
+                  bank: FilterBank | None = None):
+    """The Morlet cross-wavelet spectrum of ``x`` and ``y`` at ``scales`` (in samples):
+    ``cross_filter_bank`` with the bank of ``morlet_filters(scales, ...)``;
+    ``(Sxy, Sxx, Syy)``, ``Sxy = conj(Wx) Wy`` (Torrence & Compo 1998 section 6c with the
+    project's conjugation), ``Sxx`` and ``Syy`` the two scalograms."""
+    if not isinstance(x, torch.Tensor) or not isinstance(y, torch.Tensor):
+        raise TypeError("x and y must be torch.Tensors")
+    _gpu_only(x, "wavelet")
+    _gpu_only(y, "wavelet")
+    return cross_filter_bank(x, y, _morlet_bank(scales, x, w0, support, nfft, bank), hop, mean)
+
+
+def smoothing_windows(scales, hop: int, cycles: float = 3.0, w0: float = W0) -> np.ndarray:
+    """The time smoothing of wavelet coherence in hop windows, host int64 ``[S]``:
+    ``n_s = 2 floor(cycles period_s / (2 hop)) + 1`` with ``period_s = 1 /
+    scale_to_frequency(s)`` samples, odd and at least 1: a length proportional to the scale
+    (Torrence & Webster 1999), without which the coherence of any two signals is 1."""
+    if int(hop) != hop or hop < 1:
+        raise ValueError(f"hop must be a positive integer, got {hop}")
+    if not cycles >= 0:
+        raise ValueError("cycles must be >= 0")
+    period = 1.0 / scale_to_frequency(scales, 1.0, w0)
+    return 2 * np.floor(cycles * period / (2.0 * int(hop))).astype(np.int64) + 1
+
+
+def _boxcar(v: torch.Tensor, widths) -> torch.Tensor:
+    """``v[..., S, T]`` smoothed along the last axis, row ``s`` by a centred boxcar of the odd
+    length ``widths[s]``, truncated at the ends and normalised by the count of values present;
+    cumulative sums in float64 (complex128). Returns the wide dtype."""
+    T = v.shape[-1]
+    wide = v.to(torch.complex128 if v.is_complex() else torch.float64)
+    c = torch.cat([torch.zeros_like(wide[..., :1]), wide.cumsum(-1)], dim=-1)  # [..., S, T + 1]
+    half = torch.as_tensor(np.asarray(widths, dtype=np.int64) // 2, device=v.device)[:, None]
+    j = torch.arange(T, device=v.device)[None, :]
+    lo = (j - half).clamp(min=0)           # [S, T]
+    hi = (j + half + 1).clamp(max=T)
+    lo_b, hi_b = lo.expand(v.shape), hi.expand(v.shape)
+    return (c.gather(-1, hi_b) - c.gather(-1, lo_b)) / (hi - lo).to(torch.float64)
+
+
+def _smooth_widths(smooth, scales, hop, w0):
+    S = _scales(scales).size
+    if smooth is None:
+        return smoothing_windows(scales, hop, w0=w0)
+    n = np.asarray(smooth)
+    if n.ndim == 0:
+        n = np.full(S, n)
+    if (n.shape != (S,) or not np.issubdtype(n.dtype, np.number) or (n != np.floor(n)).any()
+            or (n < 1).any() or (n.astype(np.int64) % 2 != 1).any()):
+        raise ValueError("smooth must be None, an odd positive integer or [S] of them")
+    return n.astype(np.int64)
+
+
+def wavelet_coherence(x: torch.Tensor, y: torch.Tensor, scales, hop: int = 1, smooth=None,
+                      w0: float = W0, support: float = SUPPORT, nfft=None,
+                      bank: FilterBank | None = None):
+    """Wavelet coherence and phase of ``x`` and ``y`` (Torrence & Webster 1999; Grinsted et al.
+    2004): ``(coh, phase, Sxy)``, float32, float32 and complex64 ``[..., S, length // hop]``.
+
+    The three mean spectra of ``cross_wavelet(mean=True)`` are smoothed along time by a centred
+    sliding boxcar of ``n_s`` hop windows at scale ``s``, truncated at the ends and normalised
+    by the count of windows present (in torch, by cumulative sums in float64). ``smooth``: None
+    for ``smoothing_windows(scales, hop)``, an odd integer for every scale, or ``[S]`` of them;
+    1 means no smoothing beyond the hop mean. Then ``coh = min(1, |Sxy|^2 / (Sxx Syy))``, 0
+    where ``Sxx Syy == 0``, and ``phase = angle(Sxy)``; ``Sxy`` is returned smoothed. Phase over
+    probe separation is the mode number."""
+    widths = _smooth_widths(smooth, scales, hop, w0)
+    sxy, sxx, syy = cross_wavelet(x, y, scales, hop, True, w0, support, nfft, bank)
+    sxy, sxx, syy = _boxcar(sxy, widths), _boxcar(sxx, widths), _boxcar(syy, widths)
+    den = sxx * syy
+    num = sxy.real * sxy.real + sxy.imag * sxy.imag
+    coh = torch.where(den > 0, num / den.clamp(min=torch.finfo(torch.float64).tiny), 0.0)
+    return (coh.clamp(max=1.0).float(), torch.angle(sxy).float(), sxy.to(torch.complex64))
