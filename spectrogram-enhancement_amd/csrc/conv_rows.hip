@@ -83,6 +83,13 @@ struct RC {
   static constexpr int PIX = CIN * 2;                 // bytes per pixel
   static constexpr int ROWB = (W + 4) * PIX;          // ring row: 2 zero pixels each side
   static constexpr int RING = 8;                      // rows (4 steps)
+  // The step timeline's constants (restated and checked on the host by
+  // tests/test_conv_rows_sched_model.py): a step issues the DMA of the rows LEAD steps ahead
+  // and waits at its end for the DMA issued one step earlier (rows LEAD - 1 ahead); the
+  // prefetching schedule (SCHED = 1) reads the fragments of the step PF ahead.
+  static constexpr int LEAD = 3;
+  static constexpr int PF = 1;
+  static_assert(2 * (LEAD + 1) <= RING && PF < LEAD - 1, "ring slots live: steps s - 1 + PF .. s + LEAD");
   static constexpr int LDS = RING * ROWB;
   static constexpr int NW = CIN == 16 ? 13 : K * K;   // resident weight fragments
   static_assert(K == 5 || (CIN == 32 && (K == 3 || K == 5)), "kernel size");
@@ -104,13 +111,73 @@ struct CRArgs {
   int lgb;           // convT row sweeps: log2 of the row bands per image (0: whole images)
 };
 
+#ifdef SPECENH_CR_STATS  // development build (tools/cr_stats.py): per-wave clocks of a step's segments
+__device__ unsigned long long cr_stats[1024 * 8 * 8];
+struct CRClock {
+  long long last = 0, seg[6] = {0, 0, 0, 0, 0, 0}, n = 0;
+  // SEG: 0 pool + store head, 1 DMA issue, 2 fragment reads until the first MFMA can issue,
+  // 3 MFMA block, 4 vmcnt wait, 5 barrier wait; -1 starts the clock
+  template <int SEG>
+  __device__ __forceinline__ void mark() {
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    const long long t = __builtin_amdgcn_s_memtime();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (SEG >= 0) seg[SEG] += t - last;
+    if constexpr (SEG == 5) ++n;
+    last = t;
+  }
+  __device__ void flush(int wv) {
+    if ((threadIdx.x & 63) == 0 && blockIdx.x < 1024) {
+      unsigned long long* p = cr_stats + (blockIdx.x * 8 + wv) * 8;
+#pragma unroll
+      for (int i = 0; i < 6; ++i) p[i] = seg[i];
+      p[6] = n;
+      p[7] = 0;
+    }
+  }
+};
+#define CR_MARK(SEG) clk.mark<SEG>()
+#else
+#define CR_MARK(SEG) ((void)0)
+#endif
+
 // K (CIN = 32 only): the kernel size, 5 (the reference model) or 3 (hyperparam_scan.py's
 // k = 3 model): K^2 resident tap fragments, K B fragments per input row, output rows
 // r + K/2 - ky; the accumulator ring of 6 rows and the pooling lag are the same.
-template <typename T, int CIN, int COUT, int W, int K = 5>
+//
+// SCHED: the step's schedule. Every wave runs the same program and all eight meet at one
+// barrier per step, so whatever a wave does with the matrix pipe empty, its SIMD partner
+// (wave w + 4) does at the same moment.
+//  0 (variant CONV_ROWS_SCHED=0; the default until round 7, kept as the A/B and bitwise
+//    partner): after the barrier every wave pools and stores pair s - 2, the DMA waves issue
+//    the rows of step s + LEAD, all B fragments of step s are read, and only when they have
+//    landed do the MFMAs start; then vmcnt(1) / vmcnt(0) — on waves 4-7 a wait for their own
+//    pooled store — and the barrier.
+//  1 (CIN = 32, K = 5, 256-VGPR build): the fragments of step s + PF are read during step
+//    s into a second register buffer (their rows were waited for at the end of step s - 1
+//    and their ring slots are refilled from step s + 2 on), so the MFMAs start right after
+//    the barrier; the MFMAs into the four accumulators that were NOT just pooled go first and
+//    the pool, pack and store run in their shadow (each accumulator keeps its (j, kx, ky)
+//    order: bitwise equal to 0); the store's address advances by scalar adds; and only the
+//    DMA waves wait on vmcnt, for the DMA they need, by the ledger of convt_rows_kernel;
+//    and the counters, addresses and branch flags of step s + 1 are computed under step s's
+//    MFMAs, so a step opens with a flag test instead of ~35 scalar instructions.
+//    Unrolled by 6: accumulator slots (s mod 3) and fragment buffer (s mod 2) are
+//    compile-time. 252 VGPRs, no scratch (schedule 0: 180).
+//    conv3 + pool at 2048 shots: 0.141 ms against 0.159 ms (profiles/conv3_sched_ab.txt);
+//    where the clocks of a step go in either schedule: profiles/conv3_phase_clocks.txt.
+// Only <32, 64, 32, 5> is launched with schedule 1. CIN = 16 cannot read a step ahead as it
+// stands: its F fragment pairs row r + 1, a row of step s + 2 when read in step s, which
+// has not been waited for then. <32, 32, 64> (K = 5: a 256-VGPR build like the flagship;
+// K = 3: 94 of 128 VGPRs) would compile, but neither is on the bench's path and neither has
+// been timed with it, so both keep the step they were measured with.
+template <typename T, int CIN, int COUT, int W, int K = 5, int SCHED = 0>
 __global__ __launch_bounds__((RC<CIN, COUT, W, K>::THREADS))
 __attribute__((amdgpu_waves_per_eu(RC<CIN, COUT, W, K>::WPE)))
 void conv_rows_pool_kernel(CRArgs a) {
+  static_assert(SCHED == 0 || (SCHED == 1 && CIN == 32), "schedule");
   using C = RC<CIN, COUT, W, K>;
   extern __shared__ __attribute__((aligned(16))) unsigned char ring[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -217,6 +284,179 @@ void conv_rows_pool_kernel(CRArgs a) {
   auto adv = [&](int& il, int& q) {
     if (++q == SPI) { q = 0; ++il; }
   };
+#ifdef SPECENH_CR_STATS
+  CRClock clk;
+#endif
+  if constexpr (SCHED == 1) {
+    // ---- schedule 1 (header comment): fragments one step ahead, head under the MFMAs ----
+    static_assert(C::PF == 1, "two fragment buffers");
+    uint4 bf[2][2][K];
+    // row j of step t's input rows -> fragment buffer P (rows 2t, 2t + 1 sit in two
+    // consecutive ring slots, the first one even: never wrapped)
+    auto frags = [&](auto pc, auto jc, const int t) {
+      constexpr int P = decltype(pc)::value, j = decltype(jc)::value;
+      const unsigned char* rb = ring + (((2 * t) & 7) + j) * C::ROWB;
+#pragma unroll
+      for (int kx = 0; kx < K; ++kx) bf[P][j][kx] = *reinterpret_cast<const uint4*>(rb + boff[kx]);
+    };
+    using I0 = std::integral_constant<int, 0>;
+    using I1 = std::integral_constant<int, 1>;
+    frags(I0{}, I0{}, 0);
+    frags(I0{}, I1{}, 0);
+    resident_loads_landed();
+    // the pooled pair's store: wave-uniform row address (scalar adds per step) + the lane's
+    // constant byte offset
+    constexpr long long ROWO = (long long)(W / 2) * COUT * (long long)sizeof(T);
+    const unsigned ovo = (unsigned)((((x0 + m) / 2) * COUT + 16 * nb + 4 * kg) * (int)sizeof(T));
+    unsigned char* ob = reinterpret_cast<unsigned char*>(a.out) +
+                        (((long long)blockIdx.x - G) * PHh + qA) * ROWO;  // pair (ilA, qA)
+    const long long ojump = (long long)(G - 1) * PHh * ROWO;  // (il, SPI - 1) -> (il + 1, 0)
+    // the DMA's source, likewise: this wave's row of step s + LEAD (rows 2 qS, 2 qS + 1 of
+    // image ilS), advanced by two rows per step and by the rest of the grid's images at a wrap
+    constexpr long long ROWX = (long long)W * CIN * (long long)sizeof(T);
+    const unsigned char* xs = reinterpret_cast<const unsigned char*>(a.x) +
+        (((long long)blockIdx.x + (long long)ilS * G) * H + 2 * qS + wv / C::WPR) * ROWX;
+    const long long xjump = (long long)(G - 1) * H * ROWX;  // (il, SPI - 1) -> (il + 1, 0)
+    int vmn = 0;           // this wave's vector-memory ops issued in the loop (DMAs, stores)
+    int mk0 = -1, mk1 = -1;  // vmn right after the DMA of steps s - 1 / s (-1: none)
+    // what the step's branches ask, from the counters: 1 the step has input rows, 2 pair s - 2
+    // is an output row, 4 the rows of step s + LEAD are inside an image (H is even: both rows)
+    // (a < b as the difference's sign bit: a compare turned into an integer went through a
+    // VGPR, which the scalar asm operand below cannot take)
+    auto lt = [](int x, int y) -> unsigned { return (unsigned)(x - y) >> 31; };
+    // (values that a run-time division made on the VALU, into scalar registers for good)
+    const int nimgs = __builtin_amdgcn_readfirstlane(nimg);
+    ilS = __builtin_amdgcn_readfirstlane(ilS);
+    qS = __builtin_amdgcn_readfirstlane(qS);
+    auto flags = [&]() -> unsigned {
+      return (lt(ilC, nimgs) & lt(2 * qC, H)) | ((lt(-1, ilA) & lt(ilA, nimgs) & lt(qA, PHh)) << 1) |
+             ((lt(ilS, nimgs) & lt(2 * qS, H)) << 2);
+    };
+    unsigned fl = __builtin_amdgcn_readfirstlane(flags());
+    // The counters, addresses and flags of step s + 1, computed under step s's MFMAs: after
+    // the barrier a step starts with a branch on a flag, not with ~35 scalar instructions
+    // that both waves of a SIMD run with the matrix pipe empty. The empty asm pins the
+    // results where it stands (the compiler otherwise sinks them to their uses).
+    auto next = [&]() {
+      if (++qA == SPI) { qA = 0; ++ilA; ob += ojump; } else { ob += ROWO; }
+      adv(ilC, qC);
+      if (++qS == SPI) { qS = 0; ++ilS; xs += xjump; } else { xs += 2 * ROWX; }
+      fl = __builtin_amdgcn_readfirstlane(flags());
+      asm volatile("" : "+s"(fl));
+    };
+    auto step1 = [&](auto ic, const int s) {
+      constexpr int I = decltype(ic)::value % 3, P = decltype(ic)::value & 1;
+      auto slot = [](int d) { return (2 * I + d + 12) % 6; };
+      using PN = std::integral_constant<int, P ^ 1>;
+      // (1) rows of step s + LEAD into the ring
+      mk1 = -1;
+      if (dma_wave) {
+        unsigned char* dst = ring + ((2 * (s + C::LEAD) + wv / C::WPR) & 7) * C::ROWB + ddst;
+        if (fl & 4u) {
+          lds_dma16_s(xs, 2u * dsrc, dst);
+          mk1 = ++vmn;
+        } else {
+          *reinterpret_cast<uint4*>(dst + 16 * lane) = uint4{0u, 0u, 0u, 0u};
+        }
+      }
+      CR_MARK(1);
+      f32x4& r0 = acc[slot(-4)];
+      f32x4& r1 = acc[slot(-3)];
+      const bool pst = (fl & 2u) != 0;  // pair s - 2 is an output row
+      // pair s - 2 (output rows 2q - 4, 2q - 3) is complete: pool, pack, reset
+      auto pool = [&]() {
+        float v[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = fmaxf(max_pair(fmaxf(r0[i], r1[i])), 0.f);
+        r0 = bias;
+        r1 = bias;
+        return uint2{pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3])};
+      };
+      // lanes m, m ^ 1 hold the same pooled values: both store them (no exec-mask branch)
+      auto store = [&](const uint2 pk) {
+        if (pst) {
+          gstore8_s(ob, ovo, pk);
+          ++vmn;
+        }
+      };
+      auto mm = [&](int j, int kx, int ky) {
+        f32x4& ac = acc[slot(j + K / 2 - ky)];
+        ac = mfma<T>(wf[ky * K + kx], bf[P][j][kx], ac);
+      };
+      if (fl & 1u) {
+        // first the row-0 MFMAs into the accumulators that are still summing (d <= 1); the
+        // pool and the first half of the next step's fragment reads go in their shadow
+#pragma unroll
+        for (int kx = 0; kx < K; ++kx)
+#pragma unroll
+          for (int ky = 0; ky < K; ++ky)
+            if (K / 2 - ky <= 1) mm(0, kx, ky);
+        const uint2 pk = pool();
+        frags(PN{}, I0{}, s + 1);
+        store(pk);
+        next();
+        // the other half of the reads ahead of the remaining MFMAs (the compiler barrier keeps
+        // them from being merged with the bubble path's reads below the MFMAs)
+        frags(PN{}, I1{}, s + 1);
+        asm volatile("" ::: "memory");
+        // then, per tap column, the row-0 MFMAs into the two reset accumulators with the
+        // row-1 MFMAs into the others between them, and last the row-1 MFMAs into the reset ones
+#pragma unroll
+        for (int kx = 0; kx < K; ++kx) {
+#pragma unroll
+          for (int ky = 0; ky < K; ++ky)
+            if (K / 2 - ky > 1) mm(0, kx, ky);
+#pragma unroll
+          for (int ky = 0; ky < K; ++ky)
+            if (1 + K / 2 - ky <= 1) mm(1, kx, ky);
+        }
+#pragma unroll
+        for (int kx = 0; kx < K; ++kx)
+#pragma unroll
+          for (int ky = 0; ky < K; ++ky)
+            if (1 + K / 2 - ky > 1) mm(1, kx, ky);
+      } else {  // the bubble between images (and the steps past the last rows)
+        store(pool());
+        next();
+        frags(PN{}, I0{}, s + 1);
+        frags(PN{}, I1{}, s + 1);
+      }
+      CR_MARK(3);
+      // (2) rows of step s + LEAD - 1 (DMA issued at step s - 1) have landed: the DMA waves
+      // wait for that DMA alone, the ops issued after it (up to two stores and this step's DMA)
+      // counted out; waves 4-7 never wait on vmcnt
+      if (mk0 >= 0) {
+        const int younger = vmn - mk0;
+        if (younger >= 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+        else if (younger == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+        else if (younger == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      }
+      mk0 = mk1;
+      CR_MARK(4);
+      lds_barrier();
+      CR_MARK(5);
+    };
+    CR_MARK(-1);
+    int s = 0;
+    for (; s + 6 <= S; s += 6) {
+      step1(std::integral_constant<int, 0>{}, s);
+      step1(std::integral_constant<int, 1>{}, s + 1);
+      step1(std::integral_constant<int, 2>{}, s + 2);
+      step1(std::integral_constant<int, 3>{}, s + 3);
+      step1(std::integral_constant<int, 4>{}, s + 4);
+      step1(std::integral_constant<int, 5>{}, s + 5);
+    }
+    if (s < S) step1(std::integral_constant<int, 0>{}, s);
+    if (s + 1 < S) step1(std::integral_constant<int, 1>{}, s + 1);
+    if (s + 2 < S) step1(std::integral_constant<int, 2>{}, s + 2);
+    if (s + 3 < S) step1(std::integral_constant<int, 3>{}, s + 3);
+    if (s + 4 < S) step1(std::integral_constant<int, 4>{}, s + 4);
+#ifdef SPECENH_CR_STATS
+    clk.flush(wv);
+#endif
+    return;
+  }
   // step s with I = s % 3 compile-time (the accumulator ring: output row 2q + d -> slot
   // (2 I + d) mod 6)
   auto step = [&](auto ic, const int s) {
@@ -241,8 +481,10 @@ void conv_rows_pool_kernel(CRArgs a) {
       r0 = bias;
       r1 = bias;
     }
+    CR_MARK(0);
     // (2) rows of step s + 3 into the ring
-    const bool issued = stage_at(s + 3, ilS, qS);
+    const bool issued = stage_at(s + C::LEAD, ilS, qS);
+    CR_MARK(1);
     // (3) this step's input rows
     const int il = ilC, q = qC;
     if (il < nimg && 2 * q < H) {
@@ -272,6 +514,7 @@ void conv_rows_pool_kernel(CRArgs a) {
           if (kg < 2) bT = uint4{0u, 0u, 0u, 0u};
         }
       }
+      CR_MARK(2);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
@@ -304,13 +547,17 @@ void conv_rows_pool_kernel(CRArgs a) {
     }
     // (4) rows of step s + 2 (DMA issued at step s - 1) have landed; this step's stores are
     // older than its DMA and complete too
+    CR_MARK(3);
     if (issued) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    CR_MARK(4);
     adv(ilA, qA);
     adv(ilC, qC);
     adv(ilS, qS);
     lds_barrier();
+    CR_MARK(5);
   };
+  CR_MARK(-1);
   int s = 0;
   for (; s + 3 <= S; s += 3) {
     step(std::integral_constant<int, 0>{}, s);
@@ -319,12 +566,15 @@ void conv_rows_pool_kernel(CRArgs a) {
   }
   if (s < S) step(std::integral_constant<int, 0>{}, s);
   if (s + 1 < S) step(std::integral_constant<int, 1>{}, s + 1);
+#ifdef SPECENH_CR_STATS
+  clk.flush(wv);
+#endif
 }
 
-template <typename T, int CIN, int COUT, int W, int K = 5>
+template <typename T, int CIN, int COUT, int W, int K = 5, int SCHED = 0>
 hipError_t launch_rows(const CRArgs& a, hipStream_t st) {
   using C = RC<CIN, COUT, W, K>;
-  const void* k = reinterpret_cast<const void*>(&conv_rows_pool_kernel<T, CIN, COUT, W, K>);
+  const void* k = reinterpret_cast<const void*>(&conv_rows_pool_kernel<T, CIN, COUT, W, K, SCHED>);
   static int per_cu[64] = {};
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
@@ -337,7 +587,7 @@ hipError_t launch_rows(const CRArgs& a, hipStream_t st) {
     per_cu[dev] = std::max(1, pc);
   }
   const long long grid = std::min<long long>(a.N, (long long)per_cu[dev] * device_cus());
-  SPECENH_LAUNCH((conv_rows_pool_kernel<T, CIN, COUT, W, K>), dim3((unsigned)grid),
+  SPECENH_LAUNCH((conv_rows_pool_kernel<T, CIN, COUT, W, K, SCHED>), dim3((unsigned)grid),
                  dim3(C::THREADS), C::LDS, st, a);
   return hipGetLastError();
 }
@@ -1950,6 +2200,8 @@ int conv_rows_pool(int dtype, const void* x, int N, int H, int W, int CI, const 
   if (dtype != SPECENH_DTYPE_F16 && dtype != SPECENH_DTYPE_BF16) return SPECENH_OK;
   if (CI == 16 && CO == 32 && W == 64 && K == 5)
     e = f16 ? launch_rows<_Float16, 16, 32, 64>(a, st) : launch_rows<__bf16, 16, 32, 64>(a, st);
+  else if (CI == 32 && CO == 64 && W == 32 && K == 5 && variant(V_CONV_ROWS_SCHED) != 0)
+    e = f16 ? launch_rows<_Float16, 32, 64, 32, 5, 1>(a, st) : launch_rows<__bf16, 32, 64, 32, 5, 1>(a, st);
   else if (CI == 32 && CO == 64 && W == 32 && K == 5)
     e = f16 ? launch_rows<_Float16, 32, 64, 32>(a, st) : launch_rows<__bf16, 32, 64, 32>(a, st);
   else if (CI == 32 && CO == 32 && W == 64 && K == 5)  // hyperparam_scan.py, 256 x 128 inputs
@@ -2065,3 +2317,9 @@ extern "C" int specenh_encoder2(int dtype, const void* x, int N, int H, int W, c
   if (e != hipSuccess) return set_error(SPECENH_EHIP, std::string("encoder2: ") + hipGetErrorString(e));
   return SPECENH_OK;
 }
+
+#ifdef SPECENH_CR_STATS
+extern "C" int specenh_cr_stats(void* host, int bytes) {
+  return hipMemcpyFromSymbol(host, HIP_SYMBOL(specenh::cr_stats), bytes) == hipSuccess ? 0 : -1;
+}
+#endif

@@ -44,6 +44,16 @@ __device__ __forceinline__ void gstore8(void* dst, uint2 v) {
   asm volatile("global_store_dwordx2 %0, %1, off" : : "v"(dst), "v"(v) : "memory");
 }
 
+// the same 8-byte store at a wave-uniform base (SGPR pair) + a 32-bit per-lane byte offset: a
+// kernel whose store address advances uniformly does the advance in scalar adds
+__device__ __forceinline__ void gstore8_s(void* sbase, unsigned voff, uint2 v) {
+  typedef unsigned u32x2 __attribute__((ext_vector_type(2)));  // (a register pair for "v")
+  asm volatile("global_store_dwordx2 %0, %1, %2"
+               :
+               : "v"(voff), "v"(__builtin_bit_cast(u32x2, v)), "s"(sbase)
+               : "memory");
+}
+
 // one 16-byte global store per lane, likewise ONE counted instruction, at a wave-uniform base
 // (SGPR pair) + a 32-bit per-lane byte offset + the immediate OFF: a kernel whose store
 // address advances uniformly keeps the lane part in one register for the whole launch
