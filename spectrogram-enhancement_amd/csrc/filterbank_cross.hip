@@ -5,17 +5,17 @@
 // cross-wavelet spectrum and the spectra wavelet coherence is formed from.
 //
 // The decomposition, the tables, the block length V and the zero extension are those of
-// filterbank.hip. filterbank_cross_kernel: a workgroup owns one (block, chunk of SC filters,
-// pair). It transforms the block of x and the block of y (block_fft.hpp) and keeps both spectra
-// in registers, thread t holding X[t + 256 i] and Y[t + 256 i]. Per filter it writes
+// filterbank.hip, taken from filterbank_block.hpp. filterbank_cross_kernel: a workgroup owns one
+// (block, chunk of SC filters, pair). It transforms the block of x and the block of y
+// (block_fft.hpp) and keeps both spectra in registers, thread t holding X[t + 256 i] and
+// Y[t + 256 i]. Per filter it writes
 // conj(X_k H_s[k]) into the free buffer and transforms it, copies the V outputs the block
 // yields, [Lmax, Lmax + V) of the result (conj(Wx) nfft, the inverse through the forward
 // transform), to a strip of their own, so that they survive Wy's ping-pong transform, and does
 // the same with Y in the two transform buffers. The epilogue reads the strip and Wy's result and
 // stores the block's V / hop outputs of each of the three arrays as one contiguous run.
-//   The mean of a hop window is a fixed-order sum, as in filterbank_kernel: runs of 16
-//   consecutive values summed in ascending order, then the runs in ascending order; the four
-//   partial sums of a run (re, im, xx, yy) go to the buffer Wy's transform leaves free.
+//   The mean of a hop window is hop_epilogue's fixed-order sum, as in filterbank_kernel; the
+//   four partial sums of a run (re, im, xx, yy) go to the buffer Wy's transform leaves free.
 //
 // Wx, Wy, their products and the inverse transforms never reach memory; no atomics; an element
 // depends on its own pair's samples, the tables, hop and mode only.
@@ -29,33 +29,25 @@
 
 #include "specenh_wavelet_cross.h"
 #include "runtime.hpp"
-#include "averaging.hpp"  // check_stride, launch, launched
-#include "block_fft.hpp"
+#include "averaging.hpp"  // check_stride
+#include "filterbank_block.hpp"
 
 namespace specenh {
 namespace {
 
+using namespace filterbank_block;  // the plan, the block pieces and the hop epilogue
 using block_fft::BlockFft;
-using block_fft::CT;
-using block_fft::c_mul;
 using block_fft::transform;
 
-constexpr int RUN = 16;     // values a thread sums in a row for the hop mean
-constexpr int MAX_SC = 16;  // filters per workgroup at most: the two forward transforms are 1/17 of its work
-constexpr int MIN_SC = 4;
 constexpr int MAX_LDS = 96 * 1024;
 
 struct Args {
   const float2* tab;  // [S + 1][nfft]: H_s, then W_nfft^n
   const float* x;
   const float* y;
-  long long xs, ys, length;
-  long long To;  // outputs per (pair, filter)
-  int S, nfft, log2n, lmax, hop;
-  int V, Vh;     // outputs of W per block, stored outputs per block (V / hop)
-  int SC, nchunk;
+  long long xs, ys;
+  Plan p;
   int mode;
-  int P;         // runs per hop window (mean mode): ceil(hop / RUN)
   float scale;   // 1 / nfft^2 (point), 1 / (nfft^2 hop) (mean)
   float2* sxy;   // [batch][S][To]
   float* sxx;    // [batch][S][To], or null together with syy
@@ -67,143 +59,78 @@ struct Args {
 __device__ __forceinline__ float2 cross(float2 fx, float2 fy) {
   return make_float2(fmaf(fx.x, fy.x, fx.y * fy.y), fmaf(fx.y, fy.x, -(fx.x * fy.y)));
 }
-__device__ __forceinline__ float power(float2 f) { return fmaf(f.x, f.x, f.y * f.y); }
 
-// one block of a signal into buf as nfft complex numbers with zero imaginary part
-template <int NI>
-__device__ __forceinline__ void load_block(float2* buf, const float* xb, long long n0,
-                                           long long length, int tid) {
-#pragma unroll
-  for (int i = 0; i < NI; ++i) {
-    const int k = tid + CT * i;
-    const long long t = n0 + k;
-    buf[k] = make_float2(t >= 0 && t < length ? xb[t] : 0.f, 0.f);
+// the hop epilogue's view of one filter's results fx = conj(Wx) nfft, fy = conj(Wy) nfft:
+// (re, im of conj(Wx) Wy, |Wx|^2, |Wy|^2) nfft^2, stored scaled at o, the block's first output
+struct CrossHop {
+  using Acc = float4;
+  const float2 *fx, *fy;
+  float2* sxy;
+  float *sxx, *syy;
+  long long o;
+  float sc;
+  bool autos;
+  __device__ float4 term(int i) const {
+    const float2 u = fx[i], v = fy[i];
+    const float2 p = cross(u, v);
+    return make_float4(p.x, p.y, power(u), power(v));
   }
-}
+  __device__ void store(int jj, const float4& v) const {
+    sxy[o + jj] = make_float2(v.x * sc, v.y * sc);
+    if (autos) {
+      sxx[o + jj] = v.z * sc;
+      syy[o + jj] = v.w * sc;
+    }
+  }
+};
 
 template <int NI>
 __global__ __launch_bounds__(CT) void filterbank_cross_kernel(Args a) {
   extern __shared__ __align__(16) float2 sm[];  // the partial sums are stored as float4
-  const int n = a.nfft, tid = threadIdx.x, S = a.S, hop = a.hop, lmax = a.lmax;
+  const int n = a.p.nfft, tid = threadIdx.x, S = a.p.S, hop = a.p.hop, lmax = a.p.lmax;
   float2* const strip = sm + 2 * n;  // V float2: Wx's outputs while Wy is transformed
   auto other = [&](const float2* p) { return p == sm ? sm + n : sm; };  // of the two transform buffers
-  const int q = blockIdx.x / a.nchunk, c = blockIdx.x - q * a.nchunk;
+  const int q = blockIdx.x / a.p.nchunk, c = blockIdx.x - q * a.p.nchunk;
   const long long b = blockIdx.y;
-  const long long n0 = (long long)q * a.V - lmax;  // first sample of the block
+  const long long n0 = (long long)q * a.p.V - lmax;  // first sample of the block
   const float2* tw = a.tab + (long long)S * n;
   BlockFft<NI> fft;
   if constexpr (NI >= 4) fft.init(tw, tid);
   float2 X[NI], Y[NI];
-  load_block<NI>(sm, a.x + b * a.xs, n0, a.length, tid);
+  load_block<NI>(sm, a.x + b * a.xs, n0, a.p.length, tid);
   __syncthreads();
-  float2* res = transform(fft, sm, sm + n, n, a.log2n, tw, tid);
+  float2* res = transform(fft, sm, sm + n, n, a.p.log2n, tw, tid);
 #pragma unroll
   for (int i = 0; i < NI; ++i) X[i] = res[tid + CT * i];
-  load_block<NI>(other(res), a.y + b * a.ys, n0, a.length, tid);  // X is still being read from res
+  load_block<NI>(other(res), a.y + b * a.ys, n0, a.p.length, tid);  // X is still being read from res
   __syncthreads();
-  res = transform(fft, other(res), res, n, a.log2n, tw, tid);
+  res = transform(fft, other(res), res, n, a.p.log2n, tw, tid);
 #pragma unroll
   for (int i = 0; i < NI; ++i) Y[i] = res[tid + CT * i];
   // the buffer the next product of X goes to: one that no thread still reads
   float2* cur = other(res);
-  const long long j0 = (long long)q * a.Vh;  // first stored output of the block
-  const int cnt = a.To - j0 < a.Vh ? (int)(a.To - j0) : a.Vh;  // >= 1: the grid has ceil(To / Vh) blocks
-  const int s1 = (c + 1) * a.SC < S ? (c + 1) * a.SC : S;
-  const float sc = a.scale;
+  const long long j0 = (long long)q * a.p.Vh;  // first stored output of the block
+  const int cnt = a.p.To - j0 < a.p.Vh ? (int)(a.p.To - j0) : a.p.Vh;  // >= 1: the grid has ceil(To / Vh) blocks
+  const int s1 = (c + 1) * a.p.SC < S ? (c + 1) * a.p.SC : S;
   const bool autos = a.sxx != nullptr;  // uniform
   float2 H[NI];  // this filter's row; the next one's is loaded under Wy's transform
-#pragma unroll
-  for (int i = 0; i < NI; ++i) H[i] = a.tab[(long long)(c * a.SC) * n + tid + CT * i];
-  for (int s = c * a.SC; s < s1; ++s) {  // uniform
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      const float2 p = c_mul(X[i], H[i]);
-      cur[tid + CT * i] = make_float2(p.x, -p.y);
-    }
+  load_row<NI>(H, a.tab, c * a.p.SC, n, tid);
+  for (int s = c * a.p.SC; s < s1; ++s) {  // uniform
+    store_product<NI>(cur, X, H, tid);
     __syncthreads();  // every thread is done with the previous filter's buffers
-    float2* rx = transform(fft, cur, other(cur), n, a.log2n, tw, tid);
+    float2* rx = transform(fft, cur, other(cur), n, a.p.log2n, tw, tid);
     // Wx's outputs to the strip (the previous filter's were last read before the barrier
     // above), the product of Y beside them; rx's transform ended on a barrier
-    for (int k = tid; k < a.V; k += CT) strip[k] = rx[lmax + k];
+    for (int k = tid; k < a.p.V; k += CT) strip[k] = rx[lmax + k];
     float2* py = other(rx);
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      const float2 p = c_mul(Y[i], H[i]);
-      py[tid + CT * i] = make_float2(p.x, -p.y);
-    }
-    if (s + 1 < s1) {
-#pragma unroll
-      for (int i = 0; i < NI; ++i) H[i] = a.tab[(long long)(s + 1) * n + tid + CT * i];
-    }
+    store_product<NI>(py, Y, H, tid);
+    if (s + 1 < s1) load_row<NI>(H, a.tab, s + 1, n, tid);
     __syncthreads();  // the strip is whole, rx is free
-    float2* ry = transform(fft, py, rx, n, a.log2n, tw, tid);
-    float2* spare = other(ry);
-    const float2* fx = strip;      // conj(Wx) * nfft at outputs q V ..
-    const float2* fy = ry + lmax;  // conj(Wy) * nfft
-    const long long o = (b * S + s) * a.To + j0;
-    cur = spare;
-    if (a.mode == SPECENH_XWT_POINT) {
-      for (int jj = tid; jj < cnt; jj += CT) {
-        const float2 u = fx[jj * hop], v = fy[jj * hop];
-        const float2 p = cross(u, v);
-        a.sxy[o + jj] = make_float2(p.x * sc, p.y * sc);
-        if (autos) {
-          a.sxx[o + jj] = power(u) * sc;
-          a.syy[o + jj] = power(v) * sc;
-        }
-      }
-    } else if (a.P == 1) {  // mean over a window of at most RUN values: one thread, ascending
-      for (int jj = tid; jj < cnt; jj += CT) {
-        float re = 0.f, im = 0.f, xx = 0.f, yy = 0.f;
-        for (int i = 0; i < hop; ++i) {
-          const float2 u = fx[jj * hop + i], v = fy[jj * hop + i];
-          const float2 p = cross(u, v);
-          re += p.x;
-          im += p.y;
-          xx += power(u);
-          yy += power(v);
-        }
-        a.sxy[o + jj] = make_float2(re * sc, im * sc);
-        if (autos) {
-          a.sxx[o + jj] = xx * sc;
-          a.syy[o + jj] = yy * sc;
-        }
-      }
-    } else {  // runs of RUN values into the free buffer, then the runs of a window, ascending
-      float4* part = reinterpret_cast<float4*>(spare);  // cnt * P <= V / 8 float4 <= nfft / 2
-      const int P = a.P;
-      for (int idx = tid; idx < cnt * P; idx += CT) {
-        const int jj = idx / P, p = idx - jj * P;
-        const int i1 = (p + 1) * RUN < hop ? (p + 1) * RUN : hop;
-        float re = 0.f, im = 0.f, xx = 0.f, yy = 0.f;
-        for (int i = p * RUN; i < i1; ++i) {
-          const float2 u = fx[jj * hop + i], v = fy[jj * hop + i];
-          const float2 pr = cross(u, v);
-          re += pr.x;
-          im += pr.y;
-          xx += power(u);
-          yy += power(v);
-        }
-        part[idx] = make_float4(re, im, xx, yy);
-      }
-      __syncthreads();
-      for (int jj = tid; jj < cnt; jj += CT) {
-        float re = 0.f, im = 0.f, xx = 0.f, yy = 0.f;
-        for (int p = 0; p < P; ++p) {
-          const float4 v = part[jj * P + p];
-          re += v.x;
-          im += v.y;
-          xx += v.z;
-          yy += v.w;
-        }
-        a.sxy[o + jj] = make_float2(re * sc, im * sc);
-        if (autos) {
-          a.sxx[o + jj] = xx * sc;
-          a.syy[o + jj] = yy * sc;
-        }
-      }
-      cur = ry;  // the partials are still being read; every thread is past the barrier, done with ry
-    }
+    float2* ry = transform(fft, py, rx, n, a.p.log2n, tw, tid);
+    // conj(Wx) * nfft at outputs q V .. in the strip, conj(Wy) * nfft in ry
+    const CrossHop h{strip, ry + lmax, a.sxy, a.sxx, a.syy, (b * S + s) * a.p.To + j0, a.scale,
+                     autos};
+    cur = hop_epilogue(h, a.mode == SPECENH_XWT_POINT, a.p.P, hop, cnt, ry, other(ry), tid);
   }
 }
 
@@ -220,47 +147,12 @@ Kernel kernel_for(int nfft) {
 
 LdsOptIn g_lds;
 
-bool allowed_nfft(int nfft) {
-  return nfft == 256 || nfft == 512 || nfft == 1024 || nfft == 2048 || nfft == 4096;
-}
-
-// the checks of specenh_filterbank that do not look at a pointer, with its messages
-int check_shape(int nscales, int nfft, int lmax, long long batch, long long length, long long hop,
+// check_shape with this entry's modes
+int check_cross(int nscales, int nfft, int lmax, long long batch, long long length, long long hop,
                 int mode) {
-  if (nscales < 1) return set_error(SPECENH_EINVAL, "nscales must be >= 1");
-  if (!allowed_nfft(nfft))
-    return set_error(SPECENH_EINVAL, "nfft must be 256, 512, 1024, 2048 or 4096");
-  if (lmax < 0 || lmax > SPECENH_FB_MAX_HALF) return set_error(SPECENH_EINVAL, "lmax must be in [0, 1024]");
-  if (batch < 0) return set_error(SPECENH_EINVAL, "batch must be >= 0");
-  if (hop < 1) return set_error(SPECENH_EINVAL, "hop must be >= 1");
-  if (2LL * lmax + hop > nfft)
-    return set_error(SPECENH_EINVAL, "2 lmax + hop must not exceed nfft");
-  if (mode != SPECENH_XWT_POINT && mode != SPECENH_XWT_MEAN)
-    return set_error(SPECENH_EINVAL, "mode must be SPECENH_XWT_POINT or SPECENH_XWT_MEAN");
-  if (length < 1) return set_error(SPECENH_EINVAL, "length must be >= 1");
-  if (mode == SPECENH_XWT_MEAN && length < hop)
-    return set_error(SPECENH_EINVAL, "signal shorter than hop");
-  return SPECENH_OK;
-}
-
-// Vh, V, To, P and the split of the filters over workgroups, for a device of `cus` compute units
-long long plan(Args& a, int nscales, int nfft, int lmax, long long batch, long long length,
-               long long hop, int mode, int cus) {
-  a.S = nscales; a.nfft = nfft; a.log2n = ilog2i(nfft); a.lmax = lmax; a.hop = (int)hop;
-  a.length = length;
-  a.Vh = (nfft - 2 * lmax) / (int)hop;  // >= 1
-  a.V = a.Vh * (int)hop;
-  a.mode = mode;
-  a.To = mode == SPECENH_XWT_MEAN ? length / hop : (length - 1) / hop + 1;
-  a.P = (a.hop + RUN - 1) / RUN;
-  const long long nblk = (a.To + a.Vh - 1) / a.Vh;
-  // filters per workgroup: as many as leave two workgroups a CU, the rule of specenh_filterbank
-  const long long want = 2LL * cus;
-  const long long nb0 = batch < 65535 ? batch : 65535;
-  a.SC = MAX_SC;
-  while (a.SC > MIN_SC && nblk * ((nscales + a.SC - 1) / a.SC) * nb0 < want) a.SC /= 2;
-  a.nchunk = (nscales + a.SC - 1) / a.SC;
-  return nblk;
+  return check_shape(nscales, nfft, lmax, batch, length, hop,
+                     mode == SPECENH_XWT_POINT || mode == SPECENH_XWT_MEAN,
+                     "mode must be SPECENH_XWT_POINT or SPECENH_XWT_MEAN", mode == SPECENH_XWT_MEAN);
 }
 
 }  // namespace
@@ -271,11 +163,12 @@ extern "C" {
 int specenh_filterbank_cross_chunk(int nscales, int nfft, int lmax, long long batch,
                                    long long length, long long hop, int mode, int cus) {
   using namespace specenh;
-  if (int rc = check_shape(nscales, nfft, lmax, batch, length, hop, mode)) return rc;
+  if (int rc = check_cross(nscales, nfft, lmax, batch, length, hop, mode)) return rc;
   if (cus < 0) return set_error(SPECENH_EINVAL, "cus must be >= 0");
-  Args a{};
-  plan(a, nscales, nfft, lmax, batch, length, hop, mode, cus > 0 ? cus : device_cus());
-  return a.SC;
+  Plan p{};
+  plan(p, nscales, nfft, lmax, batch, length, hop, mode == SPECENH_XWT_MEAN,
+       cus > 0 ? cus : device_cus());
+  return p.SC;
 }
 
 int specenh_filterbank_cross(const void* tables, int nscales, int nfft, int lmax, const float* x,
@@ -288,7 +181,7 @@ int specenh_filterbank_cross(const void* tables, int nscales, int nfft, int lmax
   if (!y) return set_error(SPECENH_EINVAL, "null y");
   if (reinterpret_cast<size_t>(tables) % 8)
     return set_error(SPECENH_EINVAL, "tables must be 8-byte aligned");
-  if (int rc = check_shape(nscales, nfft, lmax, batch, length, hop, mode)) return rc;
+  if (int rc = check_cross(nscales, nfft, lmax, batch, length, hop, mode)) return rc;
   if (int rc = check_stride(x_stride, length, "x_stride < length")) return rc;
   if (int rc = check_stride(y_stride, length, "y_stride < length")) return rc;
   if (!sxy) return set_error(SPECENH_EINVAL, "null sxy");
@@ -297,28 +190,26 @@ int specenh_filterbank_cross(const void* tables, int nscales, int nfft, int lmax
   Args a{};
   a.tab = reinterpret_cast<const float2*>(tables);
   a.xs = x_stride; a.ys = y_stride;
-  const long long nblk = plan(a, nscales, nfft, lmax, batch, length, hop, mode, device_cus());
+  a.mode = mode;
+  const long long nblk = plan(a.p, nscales, nfft, lmax, batch, length, hop,
+                              mode == SPECENH_XWT_MEAN, device_cus());
   const double inv = 1.0 / nfft;
   a.scale = (float)(mode == SPECENH_XWT_POINT ? inv * inv : inv * inv / (double)hop);
-  if (nblk * a.nchunk > 2147483647LL) return set_error(SPECENH_EUNSUPPORTED, "too many blocks");
+  if (nblk * a.p.nchunk > 2147483647LL) return set_error(SPECENH_EUNSUPPORTED, "too many blocks");
   hipError_t e = allow_lds(g_lds,
                            {(const void*)kernel_for(2048), (const void*)kernel_for(4096)}, MAX_LDS);
   if (e != hipSuccess)
     return set_error(SPECENH_EHIP, std::string("filterbank_cross: ") + hipGetErrorString(e));
-  const size_t lds = ((size_t)2 * nfft + a.V) * sizeof(float2);
-  const Kernel kern = kernel_for(nfft);
-  for (long long b0 = 0; b0 < batch; b0 += 65535) {  // grid.y limit
-    const long long nb = batch - b0 < 65535 ? batch - b0 : 65535;
-    const size_t at = (size_t)b0 * nscales * a.To;
-    a.x = x + b0 * x_stride;
-    a.y = y + b0 * y_stride;
-    a.sxy = reinterpret_cast<float2*>(sxy) + at;
-    a.sxx = sxx ? sxx + at : nullptr;
-    a.syy = syy ? syy + at : nullptr;
-    launch(kern, dim3((unsigned)(nblk * a.nchunk), (unsigned)nb), dim3(CT), lds, stream, a);
-    if (int rc = launched("filterbank_cross")) return rc;
-  }
-  return SPECENH_OK;
+  const size_t lds = ((size_t)2 * nfft + a.p.V) * sizeof(float2);
+  return launch_slices(kernel_for(nfft), a, nblk, batch, lds, stream, "filterbank_cross",
+                       [&](long long b0) {
+                         const size_t at = (size_t)b0 * nscales * a.p.To;
+                         a.x = x + b0 * x_stride;
+                         a.y = y + b0 * y_stride;
+                         a.sxy = reinterpret_cast<float2*>(sxy) + at;
+                         a.sxx = sxx ? sxx + at : nullptr;
+                         a.syy = syy ? syy + at : nullptr;
+                       });
 }
 
 }  // extern "C"

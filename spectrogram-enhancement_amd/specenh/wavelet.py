@@ -141,6 +141,45 @@ class FilterBank:
         return (self.nfft - 2 * self.lmax) // int(hop) * int(hop)
 
 
+def _check_call(bank, hop, mean, shape_msg, *signals) -> int:
+    """The checks filter_bank and cross_filter_bank make alike, in their order: the bank, the
+    signals' ``[..., length]`` shape (one length), hop, the block and the length. Returns the
+    length."""
+    if not isinstance(bank, FilterBank):
+        raise TypeError("bank must be a FilterBank")
+    if any(v.dim() < 1 or v.shape[-1] != signals[0].shape[-1] for v in signals):
+        raise ValueError(shape_msg)
+    if int(hop) != hop or hop < 1:
+        raise ValueError(f"hop must be a positive integer, got {hop}")
+    if 2 * bank.lmax + hop > bank.nfft:
+        raise ValueError(f"2 lmax + hop must not exceed nfft: 2 * {bank.lmax} + {hop} > "
+                         f"{bank.nfft}")
+    L = signals[0].shape[-1]
+    if L < 1 or (mean and L < hop):
+        raise ValueError(f"signal of {L} samples is shorter than " +
+                         (f"hop = {hop}" if L else "one sample"))
+    return L
+
+
+def _check_device(bank, **signals):
+    """Every signal on a ROCm device, and on the bank's."""
+    for v in signals.values():
+        _gpu_only(v, "wavelet")
+    if any(v.device != bank.device for v in signals.values()):
+        where = ", ".join(f"{n} on {v.device}" for n, v in signals.items())
+        raise ValueError(f"{where}, the bank on {bank.device}".replace(" on ", " is on ", 1))
+
+
+def _rows(v, lead, L):
+    """``v`` broadcast to ``lead + (L,)`` as float32 rows ``[B, L]`` the kernels can stride."""
+    v = v.expand(lead + (L,)).reshape(-1, L)
+    if v.dtype != torch.float32:
+        v = v.float()
+    if v.stride(1) != 1 or (v.shape[0] > 1 and v.stride(0) < L):
+        v = v.contiguous()  # a broadcast signal (stride 0) is materialised
+    return v
+
+
 def filter_bank(x: torch.Tensor, bank: FilterBank, hop: int = 1, mode: str = "complex"):
     """``bank`` applied to ``x[..., length]`` on a ROCm device: ``[..., S, To]``, complex64
     ``W[.., j hop]`` (``mode="complex"``), float32 ``|W[.., j hop]|^2`` (``"power"``), both with
@@ -152,29 +191,10 @@ def filter_bank(x: torch.Tensor, bank: FilterBank, hop: int = 1, mode: str = "co
         raise ValueError(f"mode must be 'complex', 'power' or 'mean_power', got {mode!r}") from None
     if not isinstance(x, torch.Tensor):
         raise TypeError("x must be a torch.Tensor")
-    if not isinstance(bank, FilterBank):
-        raise TypeError("bank must be a FilterBank")
-    if x.dim() < 1:
-        raise ValueError("x must be [..., length]")
-    if int(hop) != hop or hop < 1:
-        raise ValueError(f"hop must be a positive integer, got {hop}")
-    if 2 * bank.lmax + hop > bank.nfft:
-        raise ValueError(f"2 lmax + hop must not exceed nfft: 2 * {bank.lmax} + {hop} > "
-                         f"{bank.nfft}")
-    L = x.shape[-1]
-    if L < 1 or (kind == _lib.FB_POWER_MEAN and L < hop):
-        raise ValueError(f"signal of {L} samples is shorter than " +
-                         (f"hop = {hop}" if L else "one sample"))
-    _gpu_only(x, "wavelet")
-    if x.device != bank.device:
-        raise ValueError(f"x is on {x.device}, the bank on {bank.device}")
+    L = _check_call(bank, hop, kind == _lib.FB_POWER_MEAN, "x must be [..., length]", x)
+    _check_device(bank, x=x)
     lead = x.shape[:-1]
-    xs = x.reshape(-1, L)
-    if xs.dtype != torch.float32:
-        xs = xs.float()
-    if xs.stride(1) != 1 or (xs.shape[0] > 1 and xs.stride(0) < L):
-        xs = xs.contiguous()
-    out = torch.ops.specenh.filterbank(xs, bank.tables, bank.lmax, int(hop), kind)
+    out = torch.ops.specenh.filterbank(_rows(x, lead, L), bank.tables, bank.lmax, int(hop), kind)
     return out.reshape(lead + out.shape[1:])
 
 
@@ -218,38 +238,15 @@ def cross_filter_bank(x: torch.Tensor, y: torch.Tensor, bank: FilterBank, hop: i
     has a negative phase at the scales that carry the signal."""
     if not isinstance(x, torch.Tensor) or not isinstance(y, torch.Tensor):
         raise TypeError("x and y must be torch.Tensors")
-    if not isinstance(bank, FilterBank):
-        raise TypeError("bank must be a FilterBank")
-    if x.dim() < 1 or y.dim() < 1 or x.shape[-1] != y.shape[-1]:
-        raise ValueError("x and y must be [..., length] with the same length")
-    if int(hop) != hop or hop < 1:
-        raise ValueError(f"hop must be a positive integer, got {hop}")
-    if 2 * bank.lmax + hop > bank.nfft:
-        raise ValueError(f"2 lmax + hop must not exceed nfft: 2 * {bank.lmax} + {hop} > "
-                         f"{bank.nfft}")
-    L = x.shape[-1]
-    if L < 1 or (mean and L < hop):
-        raise ValueError(f"signal of {L} samples is shorter than " +
-                         (f"hop = {hop}" if L else "one sample"))
+    L = _check_call(bank, hop, mean, "x and y must be [..., length] with the same length", x, y)
     try:
         lead = torch.broadcast_shapes(x.shape[:-1], y.shape[:-1])
     except RuntimeError:
         raise ValueError(f"the leading dimensions of x {tuple(x.shape[:-1])} and y "
                          f"{tuple(y.shape[:-1])} do not broadcast") from None
-    _gpu_only(x, "wavelet")
-    _gpu_only(y, "wavelet")
-    if x.device != bank.device or y.device != bank.device:
-        raise ValueError(f"x is on {x.device}, y on {y.device}, the bank on {bank.device}")
-
-    def rows(v):
-        v = v.expand(lead + (L,)).reshape(-1, L)
-        if v.dtype != torch.float32:
-            v = v.float()
-        if v.stride(1) != 1 or (v.shape[0] > 1 and v.stride(0) < L):
-            v = v.contiguous()  # a broadcast signal (stride 0) is materialised
-        return v
-
-    out = torch.ops.specenh.filterbank_cross(rows(x), rows(y), bank.tables, bank.lmax, int(hop),
+    _check_device(bank, x=x, y=y)
+    out = torch.ops.specenh.filterbank_cross(_rows(x, lead, L), _rows(y, lead, L), bank.tables,
+                                             bank.lmax, int(hop),
                                              _lib.XWT_MEAN if mean else _lib.XWT_POINT)
     return tuple(o.reshape(lead + o.shape[1:]) for o in out)
 

@@ -378,20 +378,28 @@ def test_sign_convention_of_the_restatement():
 
 
 def test_filters_per_workgroup_restates_the_host_rule():
-    """wl.filters_per_workgroup against the text of specenh_filterbank (the kernel gives no way
-    to observe SC), its values at the MI355X's 256 CUs, and every chunk size reachable with the
-    bank of test_filters_per_workgroup_do_not_change_a_bit at any CU count a device may have."""
-    src = open(os.path.join(REPO, "spectrogram-enhancement_amd", "csrc", "filterbank.hip")).read()
-    src = " ".join(src.split())
+    """wl.filters_per_workgroup against the text of plan() in csrc/filterbank_block.hpp, the one
+    place both entries take the rule from (the single-signal kernel gives no way to observe
+    SC), its values at the MI355X's 256 CUs, and every chunk size reachable with the bank of
+    test_filters_per_workgroup_do_not_change_a_bit at any CU count a device may have."""
+    csrc = os.path.join(REPO, "spectrogram-enhancement_amd", "csrc")
+    src = " ".join(open(os.path.join(csrc, "filterbank_block.hpp")).read().split())
     for line in ("constexpr int MAX_SC = 16;", "constexpr int MIN_SC = 4;",
-                 "a.Vh = (nfft - 2 * lmax) / (int)hop;",
-                 "a.To = mode == SPECENH_FB_POWER_MEAN ? length / hop : (length - 1) / hop + 1;",
-                 "const long long nblk = (a.To + a.Vh - 1) / a.Vh;",
-                 "const long long want = 2LL * device_cus();",
+                 "p.Vh = (nfft - 2 * lmax) / (int)hop;",
+                 "p.To = mean ? length / hop : (length - 1) / hop + 1;",
+                 "const long long nblk = (p.To + p.Vh - 1) / p.Vh;",
+                 "const long long want = 2LL * cus;",
                  "const long long nb0 = batch < 65535 ? batch : 65535;",
-                 "a.SC = MAX_SC; while (a.SC > MIN_SC && nblk * ((nscales + a.SC - 1) / a.SC) "
-                 "* nb0 < want) a.SC /= 2;"):
+                 "p.SC = MAX_SC; while (p.SC > MIN_SC && nblk * ((nscales + p.SC - 1) / p.SC) "
+                 "* nb0 < want) p.SC /= 2;"):
         assert line in src, line
+    # neither entry keeps a copy; each plans for the device it runs on, with its own mean mode
+    for name, call in (("filterbank.hip", "const bool mean = mode == SPECENH_FB_POWER_MEAN;"),
+                       ("filterbank.hip", "hop, mean, device_cus());"),
+                       ("filterbank_cross.hip", "hop, mode == SPECENH_XWT_MEAN, device_cus());")):
+        hip = " ".join(open(os.path.join(csrc, name)).read().split())
+        assert "SC /= 2" not in hip and "(length - 1) / hop + 1" not in hip, name
+        assert call in hip, (name, call)
     cfg = wl.CHUNK_CFG
     assert (cfg["nfft"], cfg["lmax"], cfg["length"], cfg["S"]) == (256, 32, 401, 33)
 

@@ -196,6 +196,23 @@ def test_cross_spectrum_alone_has_the_same_bits(gpu_device, name, hop, mode):
     assert torch.equal(torch.view_as_real(alone[0]), torch.view_as_real(both[0]))
 
 
+@pytest.mark.parametrize("name", ("hop256", "hop1024"))
+def test_autos_have_the_bits_of_the_single_signal_kernel(gpu_device, name):
+    """sxx and syy equal filterbank's power (point) and mean power (mean) of x and of y bit for
+    bit, at every hop and mode of the configuration: the two kernels take the block load, the
+    product and the hop mean's summation order from csrc/filterbank_block.hpp. hop256 runs
+    fft_lds::stockham (NI = 1), hop1024 BlockFft (NI = 4)."""
+    dev = gpu_device
+    bank = bank_of(dev, name)
+    x, y = xl.pair_of(name)
+    xd, yd = strided(dev, x), strided(dev, y, PAD + 4)
+    for hop, mode in xl.cases(name):
+        _, sxx, syy = launch(xd, yd, bank, hop, mode)
+        for auto, v in ((sxx, xd), (syy, yd)):
+            alone = torch.ops.specenh.filterbank(v, bank.tables, bank.lmax, hop, xl.fb_mode(mode))
+            assert torch.equal(auto, alone), (hop, mode)
+
+
 def test_batches_above_the_grid_limit_are_sliced(gpu_device):
     """65,537 pairs of 5 samples: the pairs past the 65,535 of one launch equal the same pairs
     run alone, and the restatement."""

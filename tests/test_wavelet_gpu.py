@@ -117,8 +117,8 @@ def test_splitting_the_bank_does_not_change_a_bit(gpu_device, mode):
 def test_filters_per_workgroup_do_not_change_a_bit(gpu_device, hop, mode):
     """The filter loop at 16, 8 and 4 filters a workgroup (SC): 33 filters, three chunks of 16
     with a single filter in the last. The kernel gives no way to observe SC, so the test rests
-    on wavelet_local.filters_per_workgroup, the restatement of the rule in specenh_filterbank
-    (csrc/filterbank.hip) that tests/test_wavelet_cpu.py holds against the host code's text:
+    on wavelet_local.filters_per_workgroup, the restatement of the rule specenh_filterbank
+    plans by (csrc/filterbank_block.hpp) that tests/test_wavelet_cpu.py holds against the host code's text:
     with the device's CU count it gives the smallest batch B16 that keeps SC = 16, a batch B8
     that runs at SC = 8, and two shots at SC = 4. The first B8 and the first two shots run
     alone equal the rows of the B16 run bit for bit, and rows 0, 1 and the last of the B16 run

@@ -51,11 +51,12 @@ def n_out(length, hop, mode):
 
 
 def filters_per_workgroup(nfft, lmax, hop, mode, length, S, B, cus):
-    """SC, the filters a workgroup of filterbank_kernel loops over. The kernel gives no way to
-    observe it, so this restates the rule of the host code, specenh_filterbank in
-    csrc/filterbank.hip (a.Vh, a.To, nblk, then the `while (a.SC > MIN_SC && ...)` loop): 16,
-    halved down to 4 while the launch has fewer than two workgroups a CU. `cus` is the
-    device's compute-unit count (runtime.hpp's device_cus)."""
+    """SC, the filters a workgroup of filterbank_kernel or filterbank_cross_kernel loops over.
+    The single-signal kernel gives no way to observe it, so this restates the rule of the host
+    code, plan() in csrc/filterbank_block.hpp, which both entries call (p.Vh, p.To, nblk, then
+    the `while (p.SC > MIN_SC && ...)` loop): 16, halved down to 4 while the launch has fewer
+    than two workgroups a CU. `cus` is the device's compute-unit count (runtime.hpp's
+    device_cus)."""
     Vh = (nfft - 2 * lmax) // hop
     To = n_out(length, hop, mode)
     nblk = (To + Vh - 1) // Vh
