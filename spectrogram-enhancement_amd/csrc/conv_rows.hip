@@ -115,8 +115,10 @@ struct CRArgs {
 __device__ unsigned long long cr_stats[1024 * 8 * 8];
 struct CRClock {
   long long last = 0, seg[6] = {0, 0, 0, 0, 0, 0}, n = 0;
-  // SEG: 0 pool + store head, 1 DMA issue, 2 fragment reads until the first MFMA can issue,
-  // 3 MFMA block, 4 vmcnt wait, 5 barrier wait; -1 starts the clock
+  // SEG (conv_rows_pool_kernel): 0 pool + store head, 1 DMA issue, 2 fragment reads until the
+  // first MFMA can issue, 3 MFMA block, 4 vmcnt wait, 5 barrier wait; -1 starts the clock.
+  // (enc2_rows_kernel): 0 pool + store head (schedule 1: the storing waves' tile store), 1 DMA
+  // issue + copy shift, 2 conv1 (schedule 1: with the pool), 3 conv2, 4 vmcnt wait, 5 barrier
   template <int SEG>
   __device__ __forceinline__ void mark() {
     __builtin_amdgcn_sched_barrier(0);
@@ -1846,11 +1848,65 @@ constexpr int E2RROWS = E2R1 + 2;                  // ring + two zero rows (pari
 #define SPECENH_ENC2_STAGGER 0
 #endif
 
+constexpr int E2LDS = RC<16, 32, 64>::LDS + E2RROWS * E2ROW * 4 + 48 * 4;  // rings + biases
+// Schedule 1's pooled-row tiles: a step's pooled row (32 pixels x 32 channels, 2 KB contiguous
+// in the NHWC output), double-buffered behind the rings and the biases. Wave (wx, nb), lane
+// (m, kg) writes the 8 bytes of channels 16 nb + 4 kg .. + 3 of pixel p = (16 wx + m) / 2 (8-byte
+// chunk c8 = 4 nb + kg of the pixel's 64 bytes) at chunk c8 ^ 2 ((p >> 1) & 3): the eight
+// pixels of a ds_write_b64 lane group then cover 32 distinct banks (a plain 64-byte pitch is
+// 4-way), and 16-byte units move whole, so the read-back needs no half swap. Store wave k, lane
+// l reads the 16 bytes of output byte 1024 k + 16 l (pixel 16 k + l / 4, unit l & 3): the four
+// lanes of a pixel cover its 64 bytes, conflict-free under the ds_read_b128 lane groups.
+// (restated and checked in tests/test_enc2_stage_mapping.py)
+constexpr int E2TILE = 32 * 32 * 2;
+constexpr int E2LDS1 = E2LDS + 2 * E2TILE;
+__host__ __device__ constexpr int e2_tile_write(int p, int c8) {
+  return 64 * p + 8 * (c8 ^ (2 * ((p >> 1) & 3)));
+}
+__host__ __device__ constexpr int e2_tile_read(int k, int l) {
+  const int p = 16 * k + (l >> 2);
+  return 64 * p + 16 * ((l & 3) ^ ((p >> 1) & 3));
+}
+
+// max of two packed pairs of T as signed 16-bit integers: a non-negative T orders as its
+// bits do and every negative one sorts below +0, so max(max(x, y), 0) = round(relu(max)) of the
+// fp32 values x and y were rounded from (rounding is monotone), with -0 -> +0 as fmaxf(., 0).
+// That holds for finite values and infinities. A NaN differs: fmaxf drops it, here one with a
+// clear sign bit sorts above every number and reaches the output.
+__device__ __forceinline__ uint32_t max_s16x2(uint32_t x, uint32_t y) {
+  typedef short s2 __attribute__((ext_vector_type(2)));
+  return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s2, x),
+                                                                __builtin_bit_cast(s2, y)));
+}
+
 // WPE: waves per SIMD the register budget is cut for (4: two workgroups per CU, 128 VGPRs;
 // 2: one workgroup, 256 VGPRs)
-template <typename T, int WPE>
+//
+// SCHED: the step's schedule (variant ENC2_SCHED; as conv_rows_pool_kernel's, every wave runs
+// the same program and all eight meet at one barrier per step, so the time of a step is the
+// time one wave takes to get through it).
+//  0 (the step until round 8, kept as the A/B and bitwise partner, and the WPE = 2 build's):
+//    every step opens with the pool of pair s - 2 and its 8-byte store, whose address, like
+//    the DMA's source row, is rebuilt from (image, row) with 64-bit multiplies; the counters
+//    and image-boundary tests follow the barrier; conv1 and conv2 are separate blocks.
+//  1 (WPE = 4 only): the store base and the DMA source row are 64-bit scalar pointers
+//    advanced by adds (one per step, the jump to the workgroup's next image at a boundary); the
+//    counters and the wave-uniform tests of step s + 1 are folded into one flag word under
+//    step s's MFMAs; the pooled row goes to an LDS tile (e2_tile_write) and leaves one step
+//    later as two 1 KB whole-line stores by waves 6 and 7 (the ones with no DMA and no part of
+//    the copy shift), so no wave's step opens with a store and the DMA waves' vmcnt ledger
+//    counts DMAs only; conv2's pool and ReLU run on packed 16-bit pairs, in one block with the
+//    tile write, the bookkeeping and conv1's fragment reads; the bubble's and the image top's
+//    F fragments are zeroed by address select. The order pool, conv1, conv2 is schedule 0's,
+//    and the copy shift keeps its exec-mask branch. Every accumulator keeps its order of MFMAs
+//    and every value its roundings: for finite accumulators (and infinities) bitwise equal to
+//    0; a NaN accumulator, which schedule 0's fmaxf drops, can reach the output (max_s16x2).
+//    (A hand-ordered block with fragments read further ahead did not fit 128 VGPRs: DESIGN.md
+//    section 7.7.)
+template <typename T, int WPE, int SCHED = 0>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(WPE)))
 void enc2_rows_kernel(E2Args a) {
+  static_assert(SCHED == 0 || (SCHED == 1 && WPE == 4), "schedule");
   using C = RC<16, 32, 64>;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   unsigned char* const ring = lds;                                        // conv2 input rows
@@ -2041,6 +2097,217 @@ void enc2_rows_kernel(E2Args a) {
     q += by;
     if (q >= per) { q -= per; ++il; }
   };
+#ifdef SPECENH_CR_STATS
+  CRClock clk;
+#endif
+
+  if constexpr (SCHED == 1) {
+    // ---- schedule 1 (header comment) ----
+    unsigned char* const tile = lds + E2LDS;
+    unsigned char* const tw = tile + e2_tile_write((x0 + m) >> 1, 4 * nb + kg);
+    // (waves 6, 7; formed where used: two registers fewer to keep through the loop)
+    auto store_tile = [&](unsigned char* base, int tb) {
+      int l = lane;
+      asm volatile("" : "+v"(l));
+      const uint4 v = *reinterpret_cast<const uint4*>(tile + tb + e2_tile_read(wv & 1, l));
+      gstore16_s<0>(base, 1024u * (wv & 1) + 16u * l, v);
+    };
+    // (values that a run-time division made on the VALU, into scalar registers for good)
+    const int nimgs = __builtin_amdgcn_readfirstlane(nimg);
+    ilD = __builtin_amdgcn_readfirstlane(ilD);
+    rD = __builtin_amdgcn_readfirstlane(rD);
+    // What a step's branches and selects ask is a property of a position of the workgroup's
+    // step stream (step t = il SPI + q: image il, pair q; q = SPI - 1 = PHh is the bubble)
+    // looked at from three distances: conv1 works for t = s + 2, conv2 on t = s, the pool on
+    // t = s - 2, the tile store on t = s - 3. So the stream is walked once, two steps ahead,
+    // and three bits per position are shifted through one word: E2F_REAL the pair is inside
+    // an image of this workgroup, E2F_BUB it is a bubble, E2F_TOP it is an image's first.
+    // Position t's bits sit 3 (s + 2 - t) places up. (restated in
+    // tests/test_enc2_stage_mapping.py)
+    constexpr unsigned E2F_REAL = 1u, E2F_BUB = 2u, E2F_TOP = 4u;
+    constexpr unsigned F_PROD = E2F_REAL, F_CBUB = E2F_BUB << 6, F_CTOP = E2F_TOP << 6,
+                       F_OTOP = E2F_TOP << 12, F_HELD = E2F_REAL << 15;
+    int ilT = 0, qT = 0;  // position s + 2
+    unsigned fl = 0;
+    // (a < b as the difference's sign bit: see conv_rows_pool_kernel's schedule 1)
+    auto lt = [](int x, int y) -> unsigned { return (unsigned)(x - y) >> 31; };
+    auto push = [&]() {  // position (ilT, qT) into the word (qT <= PHh)
+      const unsigned in = lt(qT, PHh);
+      fl = (fl << 3) | ((lt(ilT, nimgs) & in) * E2F_REAL) | ((in ^ 1u) * E2F_BUB) |
+           (lt(qT, 1) * E2F_TOP);
+    };
+    auto walk = [&]() {
+      if (++qT == SPI) { qT = 0; ++ilT; }
+    };
+    push();  // t = 0 .. 2 (the positions before the stream are no pairs: zeros)
+    walk();
+    push();
+    walk();
+    push();
+    fl = __builtin_amdgcn_readfirstlane(fl);
+    // the pooled row of pair t: its 2 KB at ob, the next pair's one row on, the next image's
+    // first (n -> n + G) a constant jump from the row past an image's last. ob is pair
+    // s - 2's, obp pair s - 3's. It starts at pair SPI - 2 of the image one grid before the
+    // workgroup's first (a position of the walk, never stored to), so that the jump into
+    // position 0 is the same as every later one
+    constexpr long long ROWO = E2TILE;
+    unsigned char* ob = reinterpret_cast<unsigned char*>(a.out) +
+                        (((long long)blockIdx.x - G) * PHh + SPI - 2) * ROWO;
+    unsigned char* obp = ob - ROWO;
+    const long long ojump = (long long)(G - 1) * PHh * ROWO;
+    // this wave's image row of the DMA (row rD - 2 of image ilD: outside the image at rD = zr,
+    // the first of waves 0, 1 and the last of waves 2, 3), four rows on per step. Like ob it is
+    // a position of the walk: it points outside the tensor whenever dreal is 0 (rows -2, -1,
+    // H1, H1 + 1 and the images past the workgroup's last) and is not dereferenced then
+    constexpr long long ROWX = (long long)C1W * (long long)sizeof(T);
+    const unsigned char* xs = reinterpret_cast<const unsigned char*>(a.x) +
+        (((long long)blockIdx.x + (long long)ilD * G) * H1 + rD - 2) * ROWX;
+    const long long xjump = (long long)(G - 1) * H1 * ROWX;
+    const int zr = wv < 2 ? wv : H1 + wv;
+    auto dma_real = [&]() { return lt(ilD, nimgs) & (lt(rD, zr) | lt(zr, rD)); };
+    unsigned dreal = __builtin_amdgcn_readfirstlane(dma_real());
+    // step s + 1's positions, pointers and flags, computed under step s's MFMAs and pinned
+    // there by the empty asm: a step opens with tests of bits
+    auto next = [&]() {
+      walk();
+      push();
+      obp = ob;
+      ob += (fl & F_OTOP) ? ojump : ROWO;
+      rD += 4;
+      if (rD >= PPI) { rD -= PPI; ++ilD; xs += xjump; } else { xs += 4 * ROWX; }
+      dreal = __builtin_amdgcn_readfirstlane(dma_real());
+      fl = __builtin_amdgcn_readfirstlane(fl);
+      asm volatile("" : "+s"(fl), "+s"(dreal), "+s"(ob), "+s"(obp), "+s"(xs));
+    };
+    auto ld16 = [](const unsigned char* p) { return *reinterpret_cast<const uint4*>(p); };
+    // one (dy, cb) pair of conv1: the two fragments, then bias + the 25 taps in two MFMAs
+    struct Pair { uint4 b, b4; };
+    auto c1_read = [&](int pb, int pr) {
+      return Pair{bfrag(pb + (pr >> 1), pr & 1), bfrag4(pb + (pr >> 1) + 4, pr & 1)};
+    };
+    // running max of the pairs' outputs, ReLU folded (starts at 0), as schedule 0's (it compiles
+    // to two v_max3_f32 per value: on packed pairs it took as many instructions, with the
+    // converts, and more registers)
+    auto c1_max = [&](float (&v)[4], const f32x4& acc1) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) v[i] = fmaxf(v[i], acc1[i]);
+    };
+
+    auto step1 = [&](auto ic, const int s) {
+      constexpr int I = decltype(ic)::value % 3, P = decltype(ic)::value & 1;
+      auto slot = [](int d) { return (2 * I + d + 12) % 6; };
+      const unsigned flc = fl;  // this step's flags (next() below makes step s + 1's)
+      f32x4& r0 = acc[slot(-4)];
+      f32x4& r1 = acc[slot(-3)];
+      // (1) the pooled row that step s - 1 left in its tile: two whole-line stores
+      if (wv >= 6 && (flc & F_HELD)) store_tile(obp, (P ^ 1) * E2TILE);
+      CR_MARK(0);
+      // (2) image rows 8 steps ahead, copies 1 .. 3 of positions 4s + 16 .. 4s + 19 (as
+      // schedule 0)
+      int nd = 0;
+      if (wv < 4) {
+        uint32_t* dst = ring1 + ((4 * s + wv) & (E2R1 - 1)) * E2ROW + 4;
+        if (dreal) {
+          if (lane < 16) lds_dma16_s(xs, 16u * lane, dst);
+          nd = 1;
+        } else {
+          int z = 0;
+          asm volatile("" : "+v"(z));
+          if (lane < 16) *reinterpret_cast<uint4*>(dst + 4 * lane) = uint4{(uint32_t)z, (uint32_t)z, (uint32_t)z, (uint32_t)z};
+        }
+      }
+      shift1(4 * s + 16);
+      CR_MARK(1);
+      // (3) the arithmetic. conv2's input rows (2s, 2s + 1: ring slots rs, rs + 1, rs even)
+      // landed before the barrier: their fragments first. The F fragment of the bubble's
+      // second row and F(-1) off an image's top are read from the ring's first 16 bytes, a
+      // halo no step writes (zeros), by address select; F(-1) only in lane groups 2, 3.
+      const int rs = (2 * s) & 7;
+      const unsigned char* rb = ring + rs * C::ROWB;
+      const int pb = 4 * (s + 2) + 2 * jr;
+      // (slot 7 pairs with slot 0: foffw = foff - 8 ROWB in lane groups 2, 3)
+      const int fo1 = (flc & F_CBUB) ? 0 : (rs + 1) * C::ROWB + (rs == 6 && kg >= 2 ? foff - 8 * C::ROWB : foff);
+      const int foT = (flc & F_CTOP) && kg >= 2 ? (rs - 1) * C::ROWB + foff : 0;  // (fo = foff - ROWB there)
+      float v[4] = {0.f, 0.f, 0.f, 0.f};
+      auto c2 = [&](int j, int w, const uint4& b) {  // weight fragment w of row j: its output row
+        const int d = w < 10 ? j + 2 - w % 5 : w == 10 ? j + 2 : w == 11 ? j : j - 2;
+        acc[slot(d)] = mfma<T>(wf[w], b, acc[slot(d)]);
+      };
+      const f32x4 bias1 = *reinterpret_cast<const f32x4*>(btab + 4 * kg);
+      auto c1a = [&](const Pair& f) { return mfma<T>(v0, f.b, bias1); };
+      auto c1b = [&](const Pair& f, const f32x4& a1) { return mfma<T>(v1, f.b4, a1); };
+      {  // pair s - 2: pool on the packed pairs (rows in lane, columns across the lane pair
+         // m, m ^ 1, ReLU), reset, into the tile: unconditionally, a tile no flag marks is
+         // never stored
+        auto nbr = [](uint32_t x) {
+          return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0xB1, 0xF, 0xF, true);
+        };
+        const uint32_t p0 = max_s16x2(pack2<T>(r0[0], r0[1]), pack2<T>(r1[0], r1[1]));
+        const uint32_t p1 = max_s16x2(pack2<T>(r0[2], r0[3]), pack2<T>(r1[2], r1[3]));
+        const f32x4 bias = bias2_ld();
+        r0 = bias;
+        r1 = bias;
+        *reinterpret_cast<uint2*>(tw + P * E2TILE) =
+            uint2{max_s16x2(max_s16x2(p0, nbr(p0)), 0u), max_s16x2(max_s16x2(p1, nbr(p1)), 0u)};
+      }
+      next();
+#pragma unroll
+      for (int pr = 0; pr < 4; ++pr) {
+        const Pair f = c1_read(pb, pr);
+        c1_max(v, c1b(f, c1a(f)));
+      }
+      CR_MARK(2);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const unsigned char* rbj = rb + j * C::ROWB;
+        const uint4 b0 = ld16(rbj + boff), b2 = ld16(rbj + boff + 64);
+        const uint4 bF = j ? ld16(ring + fo1) : ld16(rbj + foff);
+#pragma unroll
+        for (int w = 0; w < 5; ++w) c2(j, w, b0);
+#pragma unroll
+        for (int w = 5; w < 10; ++w) c2(j, w, b2);
+        c2(j, 10, bF); c2(j, 11, bF); c2(j, 12, bF);
+        if (j == 0) acc[slot(1)] = mfma<T>(wf[10], ld16(ring + foT), acc[slot(1)]);
+      }
+      // conv2 input row 2 q + jr of step s + 2 into its ring slot (zeros outside the image)
+      {
+        const uint2 pv = uint2{pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3])};
+        const uint32_t keep = 0u - (flc & F_PROD);
+        *reinterpret_cast<uint2*>(ring + ((2 * s + 4 + jr) & 7) * C::ROWB + (16 * w1x + m + 2) * 32 +
+                                  8 * kg) = uint2{pv.x & keep, pv.y & keep};
+      }
+      CR_MARK(3);
+      // (4) the DMA of step s - 3 has landed: wait for all but the DMAs issued after it (the
+      // DMA waves issue nothing else)
+      if (wv < 4) wait_vmcnt_ss<3>(c_2 + c_1 + nd);
+      c_2 = c_1;
+      c_1 = nd;
+      CR_MARK(4);
+      lds_barrier();
+      CR_MARK(5);
+    };
+    const int Ss = __builtin_amdgcn_readfirstlane(S);
+    CR_MARK(-1);
+    for (int s = 0; s < Ss; s += 6) {
+      step1(std::integral_constant<int, 0>{}, s);
+      if (s + 1 >= Ss) break;
+      step1(std::integral_constant<int, 1>{}, s + 1);
+      if (s + 2 >= Ss) break;
+      step1(std::integral_constant<int, 2>{}, s + 2);
+      if (s + 3 >= Ss) break;
+      step1(std::integral_constant<int, 3>{}, s + 3);
+      if (s + 4 >= Ss) break;
+      step1(std::integral_constant<int, 4>{}, s + 4);
+      if (s + 5 >= Ss) break;
+      step1(std::integral_constant<int, 5>{}, s + 5);
+    }
+    // the last step's pooled row (the barrier that ended it published the tile)
+    if (wv >= 6 && (fl & F_HELD)) store_tile(obp, ((Ss - 1) & 1) * E2TILE);
+#ifdef SPECENH_CR_STATS
+    clk.flush(wv);
+#endif
+    return;
+  }
 
   auto step = [&](auto ic, const int s) {
     constexpr int I = decltype(ic)::value;
@@ -2067,12 +2334,14 @@ void enc2_rows_kernel(E2Args a) {
       r0 = bias;
       r1 = bias;
     }
+    CR_MARK(0);
     // image rows 8 steps ahead (positions 4s + 32 .. 4s + 35: slots of 4s .. 4s + 3, whose
     // last readers were this step's predecessors), copy 1 of positions 4s + 16 .. 4s + 19
     // (landed: DMA of step s - 4, waited at the end of step s - 1), conv2 input rows of
     // step s + 2 (positions 4s + 8 .. 4s + 15)
     const int nd = wv < 4 ? stage1_at(4 * s + 32 + wv, ilD, rD - 2) : 0;
     shift1(4 * s + 16);
+    CR_MARK(1);
     // this step's conv2 rows, unconditionally: past an image they are the zero rows the
     // conv1 stage stored (adding nothing)
     const int q = qC;
@@ -2120,8 +2389,10 @@ void enc2_rows_kernel(E2Args a) {
       produce(s + 2, ilB, qB);
     } else {
       produce(s + 2, ilB, qB);
+      CR_MARK(2);
       conv2_rows();
     }
+    CR_MARK(3);
     // the DMA of step s - 3 (copy-1 shifted at step s + 1) must have landed: wait for all
     // but this wave's vector-memory ops of steps s - 2 .. s (each step: its store, then its
     // DMA). Only the DMA waves wait; stores alone are never waited for.
@@ -2145,8 +2416,11 @@ void enc2_rows_kernel(E2Args a) {
     qC = qC + 1 == SPI ? 0 : qC + 1;
     adv(ilB, qB, 1, SPI);
     adv(ilD, rD, 4, PPI);
+    CR_MARK(4);
     lds_barrier();
+    CR_MARK(5);
   };
+  CR_MARK(-1);
   int s = 0;
   for (; s + 3 <= S; s += 3) {
     step(std::integral_constant<int, 0>{}, s);
@@ -2155,13 +2429,15 @@ void enc2_rows_kernel(E2Args a) {
   }
   if (s < S) step(std::integral_constant<int, 0>{}, s);
   if (s + 1 < S) step(std::integral_constant<int, 1>{}, s + 1);
+#ifdef SPECENH_CR_STATS
+  clk.flush(wv);
+#endif
 }
 
-constexpr int E2LDS = RC<16, 32, 64>::LDS + E2RROWS * E2ROW * 4 + 48 * 4;
-
-template <typename T, int WPE>
+template <typename T, int WPE, int SCHED>
 hipError_t launch_enc2_wpe(const E2Args& a, hipStream_t st) {
-  const void* k = reinterpret_cast<const void*>(&enc2_rows_kernel<T, WPE>);
+  constexpr int LDSB = SCHED == 1 ? E2LDS1 : E2LDS;
+  const void* k = reinterpret_cast<const void*>(&enc2_rows_kernel<T, WPE, SCHED>);
   static int per_cu[64] = {};
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
@@ -2169,18 +2445,23 @@ hipError_t launch_enc2_wpe(const E2Args& a, hipStream_t st) {
   if (dev < 0 || dev >= 64) dev = 0;
   if (per_cu[dev] == 0) {
     int pc = 0;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, k, 512, E2LDS);
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, k, 512, LDSB);
     if (e != hipSuccess) return e;
     per_cu[dev] = std::max(1, pc);
   }
   const long long grid = std::min<long long>(a.N, (long long)per_cu[dev] * device_cus());
-  SPECENH_LAUNCH((enc2_rows_kernel<T, WPE>), dim3((unsigned)grid), dim3(512), E2LDS, st, a);
+  SPECENH_LAUNCH((enc2_rows_kernel<T, WPE, SCHED>), dim3((unsigned)grid), dim3(512), LDSB, st, a);
   return hipGetLastError();
 }
 
+// schedule 1 (variant ENC2_SCHED, the default) for the two-workgroups-per-CU build when the
+// output is 16-byte aligned (its whole-line stores are 16 bytes per lane); the earlier step
+// otherwise
 template <typename T>
 hipError_t launch_enc2(const E2Args& a, hipStream_t st) {
-  return variant(V_ENC2_WPE2) ? launch_enc2_wpe<T, 2>(a, st) : launch_enc2_wpe<T, 4>(a, st);
+  if (variant(V_ENC2_WPE2)) return launch_enc2_wpe<T, 2, 0>(a, st);
+  if (variant(V_ENC2_SCHED) != 0 && ((uintptr_t)a.out & 15) == 0) return launch_enc2_wpe<T, 4, 1>(a, st);
+  return launch_enc2_wpe<T, 4, 0>(a, st);
 }
 
 }  // namespace
@@ -2307,11 +2588,13 @@ extern "C" int specenh_encoder2(int dtype, const void* x, int N, int H, int W, c
   hipStream_t st = (hipStream_t)stream;
   static LdsOptIn lds_site;
   (void)allow_lds(lds_site,
-                  {reinterpret_cast<const void*>(&enc2_rows_kernel<_Float16, 4>),
-                   reinterpret_cast<const void*>(&enc2_rows_kernel<__bf16, 4>),
-                   reinterpret_cast<const void*>(&enc2_rows_kernel<_Float16, 2>),
-                   reinterpret_cast<const void*>(&enc2_rows_kernel<__bf16, 2>)},
-                  E2LDS);
+                  {reinterpret_cast<const void*>(&enc2_rows_kernel<_Float16, 4, 1>),
+                   reinterpret_cast<const void*>(&enc2_rows_kernel<__bf16, 4, 1>),
+                   reinterpret_cast<const void*>(&enc2_rows_kernel<_Float16, 4, 0>),
+                   reinterpret_cast<const void*>(&enc2_rows_kernel<__bf16, 4, 0>),
+                   reinterpret_cast<const void*>(&enc2_rows_kernel<_Float16, 2, 0>),
+                   reinterpret_cast<const void*>(&enc2_rows_kernel<__bf16, 2, 0>)},
+                  E2LDS1);
   const hipError_t e = dtype == SPECENH_DTYPE_F16 ? launch_enc2<_Float16>(a, st)
                                                   : launch_enc2<__bf16>(a, st);
   if (e != hipSuccess) return set_error(SPECENH_EHIP, std::string("encoder2: ") + hipGetErrorString(e));
