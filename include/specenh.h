@@ -381,7 +381,8 @@ int specenh_encoder2(int dtype, const void* x, int N, int H, int W, const void* 
  *   SPECENH_FILTER_MEANSUB  rescale(|x - mean of its row|)   meansub,  :58-61
  * workspace >= specenh_filter_workspace_bytes(batch, rows).
  * specenh_quantfilt: x < q(column) ? 0 : x with q the numpy 'linear' thr-quantile of each
- * column (np.quantile(src, thr, axis=0), quantfilt :46-49); rows <= 1264. */
+ * column (np.quantile(src, thr, axis=0) on an array of that dtype, quantfilt :46-49; a
+ * column with a NaN is copied unchanged); rows <= 1276 in float64, <= 2552 in float32. */
 #define SPECENH_FILTER_NORM 0
 #define SPECENH_FILTER_RESCALE 1
 #define SPECENH_FILTER_MEANSUB 2

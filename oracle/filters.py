@@ -144,8 +144,8 @@ def rescale_u8(u8: np.ndarray) -> np.ndarray:
         return (u8 - mn) / (mx - mn)
 
 
-def gaussblr(src, filt=(31, 3)):
-    return rescale_u8(gaussian_blur_u8(to_u8(src), filt))
+def gaussblr(src, filt=(31, 3), sigma: float = 0.0):
+    return rescale_u8(gaussian_blur_u8(to_u8(src), filt, sigma))
 
 
 def morph(src):

@@ -5,10 +5,14 @@
 // statistics are per spectrogram and accumulated in fp64. T = float or double: the numpy
 // API uploads the reference's float64 arrays unchanged, so the double path reproduces
 // numpy up to the order of its fp64 sums; elementwise results follow numpy's formulas in T.
-// quantfilt's per-column quantile is numpy's 'linear' method exactly: the virtual index
-// n*q + (1 - q) - 1 (numpy's alpha = beta = 1 expression, evaluated on the host), the two
-// neighbouring order statistics found by stable rank counting in LDS, numpy's two-sided
-// _lerp in fp64 (explicitly rounded operations, no contraction), then x < q ? 0 : x.
+// quantfilt's per-column quantile is numpy's 'linear' method in the array's own dtype, as
+// np.quantile(src, thr, axis=0) evaluates it: q rounded to T, the virtual index (n - 1) * q,
+// its floor and the weight in T on the host, the two neighbouring order statistics found by
+// stable rank counting in LDS, numpy's two-sided _lerp in T, then x < q ? 0 : x compared in
+// T. A column that holds a NaN has the quantile NaN and is copied unchanged. One caveat: the
+// float64 lerp is compiled to fused multiply-adds, so where diff * t is inexact q can sit one
+// ulp from numpy's; that shows only if an element of the column equals one of the two values
+// (statistics a few ulps apart). The float32 lerp is not fused.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -44,15 +48,17 @@ __device__ void block_minmax(double& mn, double& mx, double* red) {
 template <typename T>
 __global__ __launch_bounds__(256) void rowmean_kernel(const T* S, long long batch, int rows,
                                                       int cols, long long stride, double* rm) {
-  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= batch * rows) return;
-  const long long b = row / rows;
-  const int r = (int)(row - b * rows);
-  const T* p = S + b * stride + (long long)r * cols;
-  double acc = 0.0;
-  for (int c = threadIdx.x & 63; c < cols; c += 64) acc += (double)p[c];
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) rm[row] = acc / (double)cols;
+  const long long nrows = batch * rows;
+  for (long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); row < nrows;
+       row += (long long)gridDim.x * 4) {  // the grid is capped: wave-uniform stride loop
+    const long long b = row / rows;
+    const int r = (int)(row - b * rows);
+    const T* p = S + b * stride + (long long)r * cols;
+    double acc = 0.0;
+    for (int c = threadIdx.x & 63; c < cols; c += 64) acc += (double)p[c];
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) rm[row] = acc / (double)cols;
+  }
 }
 
 // per-spectrogram statistics: NORM {mean, std}; RESCALE {min, max}; MEANSUB {min, max} of
@@ -123,19 +129,41 @@ __global__ __launch_bounds__(256) void apply_kernel(const T* S, T* out, long lon
 constexpr int QF_COLS = 16;  // columns per workgroup
 constexpr int QF_MAX_LDS = 160 * 1024 - 512;  // largest column block (dynamic LDS) accepted
 
+// numpy's _lerp(a, b, t) in the array's dtype. The float32 one rounds every operation on
+// its own, as numpy's separate ufunc calls do. The float64 one is the expression this file
+// has always had: the compiler contracts its multiply-add pairs, which can move q by one
+// ulp when the product is inexact; its results are kept bit for bit.
+__device__ __forceinline__ double np_lerp(double a, double b, double t) {
+  const double diff = __dsub_rn(b, a);
+  return t >= 0.5 ? __dsub_rn(b, __dmul_rn(diff, __dsub_rn(1.0, t)))
+                  : __dadd_rn(a, __dmul_rn(diff, t));
+}
+__device__ __forceinline__ float np_lerp(float a, float b, float t) {
+#pragma clang fp contract(off)
+  const float diff = b - a;
+  const float up = diff * t, down = diff * (1.0f - t);
+  return t >= 0.5f ? b - down : a + up;
+}
+
 // quantfilt: order statistics lo/hi of each column by stable rank counting, numpy's lerp,
-// threshold. Columns of the tile live column-major in LDS.
+// threshold. Columns of the tile live column-major in LDS. A column that holds a NaN has
+// no order statistics to speak of: numpy's quantile of it is NaN, nothing compares below
+// NaN, and the column passes through unchanged.
 template <typename T>
 __global__ __launch_bounds__(256) void quantfilt_kernel(const T* S, T* out, int rows, int cols,
                                                         long long stride, int lo, int hi,
-                                                        double gamma) {
+                                                        T gamma) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   T* col = reinterpret_cast<T*>(smem);  // [QF_COLS][rows]
-  __shared__ double sel[QF_COLS][2];
+  __shared__ T sel[QF_COLS][2];
+  __shared__ int has_nan[QF_COLS];
+  static_assert(sizeof(sel) + sizeof(has_nan) <= 160 * 1024 - QF_MAX_LDS,
+                "static LDS must fit in what QF_MAX_LDS leaves of the CU's 160 KiB");
   const long long b = blockIdx.y;
   const int c0 = blockIdx.x * QF_COLS;
   const int nc = min(QF_COLS, cols - c0);
   const T* s = S + b * stride;
+  if (threadIdx.x < QF_COLS) has_nan[threadIdx.x] = 0;
   for (int idx = threadIdx.x; idx < rows * QF_COLS; idx += 256) {
     const int r = idx / QF_COLS, c = idx - (idx / QF_COLS) * QF_COLS;
     col[c * rows + r] = c < nc ? s[(long long)r * cols + c0 + c] : (T)0;
@@ -145,23 +173,25 @@ __global__ __launch_bounds__(256) void quantfilt_kernel(const T* S, T* out, int 
     const int c = idx / rows, i = idx - (idx / rows) * rows;
     const T* v = col + c * rows;
     const T vi = v[i];
+    if (vi != vi) {  // NaN: every thread that sees one stores the same flag
+      has_nan[c] = 1;
+      continue;
+    }
     int rank = 0;
     for (int j = 0; j < rows; ++j) {
       const T vj = v[j];
       rank += (vj < vi) || (vj == vi && j < i);
     }
-    if (rank == lo) sel[c][0] = (double)vi;
-    if (rank == hi) sel[c][1] = (double)vi;
+    if (rank == lo) sel[c][0] = vi;
+    if (rank == hi) sel[c][1] = vi;
   }
   __syncthreads();
   for (int idx = threadIdx.x; idx < rows * nc; idx += 256) {
     const int r = idx / nc, c = idx - (idx / nc) * nc;
-    const double a = sel[c][0], bb = sel[c][1];
-    const double diff = __dsub_rn(bb, a);  // numpy _lerp, :4653-4657
-    const double q = gamma >= 0.5 ? __dsub_rn(bb, __dmul_rn(diff, __dsub_rn(1.0, gamma)))
-                                  : __dadd_rn(a, __dmul_rn(diff, gamma));
     const T x = col[c * rows + r];
-    out[b * stride + (long long)r * cols + c0 + c] = ((double)x < q) ? (T)0 : x;
+    bool below = false;  // x < NaN
+    if (!has_nan[c]) below = x < np_lerp(sel[c][0], sel[c][1], gamma);  // ranks all written
+    out[b * stride + (long long)r * cols + c0 + c] = below ? (T)0 : x;
   }
 }
 
@@ -309,9 +339,30 @@ int run_filter(int op, const T* S, long long batch, int rows, int cols, long lon
   return hipGetLastError() == hipSuccess ? SPECENH_OK : set_error(SPECENH_EHIP, "filter launch");
 }
 
+// numpy 'linear': the virtual index (n - 1) * q, its neighbours lo/hi and the lerp weight
+// gamma (_quantile), all in the array's dtype T: numpy rounds q to the dtype of a floating
+// array first. thr is in [0, 1], so the index is never negative.
 template <typename T>
-int run_quantfilt(const T* S, long long batch, int rows, int cols, long long stride, int lo,
-                  int hi, double gamma, T* out, hipStream_t st) {
+void quantile_index(int rows, double thr, int& lo, int& hi, T& gamma) {
+  const T last = (T)(rows - 1);
+  const T vi = last * (T)thr;
+  if (vi >= last) {
+    lo = hi = rows - 1;
+    gamma = (T)0;  // a == b: the lerp returns the maximum
+  } else {
+    const T fl = std::floor(vi);
+    lo = (int)fl;
+    hi = lo + 1;
+    gamma = vi - fl;  // exact
+  }
+}
+
+template <typename T>
+int run_quantfilt(const T* S, long long batch, int rows, int cols, long long stride, double thr,
+                  T* out, hipStream_t st) {
+  int lo, hi;
+  T gamma;
+  quantile_index(rows, thr, lo, hi, gamma);
   const size_t lds = (size_t)rows * QF_COLS * sizeof(T);
   static LdsOptIn lds_site;
   if (allow_lds(lds_site, {(const void*)quantfilt_kernel<T>}, QF_MAX_LDS) != hipSuccess)
@@ -462,31 +513,18 @@ int specenh_quantfilt(int dtype, const void* S, long long batch, int rows, int c
                       long long stride, double thr, void* out, void* stream) {
   if (int e = check_common(dtype, S, batch, rows, cols, stride, out)) return e;
   if (!(thr >= 0.0 && thr <= 1.0)) return set_error(SPECENH_EINVAL, "Quantiles must be in the range [0, 1]");
-  if ((size_t)rows * QF_COLS * (dtype == SPECENH_DTYPE_F64 ? 8 : 4) > QF_MAX_LDS)
-    return set_error(SPECENH_EUNSUPPORTED, "quantfilt on the GPU needs rows <= 1264");
+  const bool f64 = dtype == SPECENH_DTYPE_F64;
+  const int max_rows = QF_MAX_LDS / (QF_COLS * (f64 ? 8 : 4));  // 16 columns in LDS
+  if (rows > max_rows)
+    return set_error(SPECENH_EUNSUPPORTED,
+                     "quantfilt on the GPU needs rows <= " + std::to_string(max_rows) +
+                         (f64 ? " for float64" : " for float32"));
   if (batch == 0) return SPECENH_OK;
-  // numpy 'linear' (alpha = beta = 1): virtual index, neighbours, gamma (_quantile)
-  const double vi = (double)rows * thr + (1.0 + thr * (1.0 - 1.0 - 1.0)) - 1.0;
-  int lo, hi;
-  double gamma;
-  if (vi >= rows - 1) {
-    lo = hi = rows - 1;
-    gamma = 0.0;  // a == b: the lerp returns the maximum
-  } else if (vi < 0) {
-    lo = hi = 0;
-    gamma = 0.0;
-  } else {
-    const double fl = std::floor(vi);
-    lo = (int)fl;
-    hi = lo + 1;
-    gamma = vi - fl;
-  }
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == SPECENH_DTYPE_F64)
-    return run_quantfilt<double>((const double*)S, batch, rows, cols, stride, lo, hi, gamma,
-                                 (double*)out, st);
-  return run_quantfilt<float>((const float*)S, batch, rows, cols, stride, lo, hi, gamma,
-                              (float*)out, st);
+  if (f64)
+    return run_quantfilt<double>((const double*)S, batch, rows, cols, stride, thr, (double*)out,
+                                 st);
+  return run_quantfilt<float>((const float*)S, batch, rows, cols, stride, thr, (float*)out, st);
 }
 
 size_t specenh_u8filter_workspace_bytes(long long batch, int rows, int cols) {

@@ -2,8 +2,8 @@
 against the reference's own outputs (tests/golden/filters.npz, made by the reference's
 functions) and the numpy restatement (oracle/filters.py).
 
-Tolerances: quantfilt is exact (same order statistics, numpy's lerp reproduced in fp64,
-then a comparison: bit-identical output); rescale is exact (min/max are exact);
+Tolerances: quantfilt is exact (same order statistics, numpy's lerp reproduced in the array's
+dtype, then a comparison: bit-identical output); rescale is exact (min/max are exact);
 norm / meansub reorder fp64 sums: max |delta| <= 1e-12 of the output range."""
 import numpy as np
 import pytest
