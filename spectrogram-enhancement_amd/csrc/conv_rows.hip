@@ -118,7 +118,7 @@ struct CRClock {
   // SEG (conv_rows_pool_kernel): 0 pool + store head, 1 DMA issue, 2 fragment reads until the
   // first MFMA can issue, 3 MFMA block, 4 vmcnt wait, 5 barrier wait; -1 starts the clock.
   // (enc2_rows_kernel): 0 pool + store head (schedule 1: the storing waves' tile store), 1 DMA
-  // issue + copy shift, 2 conv1 (schedule 1: with the pool), 3 conv2, 4 vmcnt wait, 5 barrier
+  // issue, 2 conv1 (schedule 1: with the pool), 3 conv2, 4 vmcnt wait, 5 barrier
   template <int SEG>
   __device__ __forceinline__ void mark() {
     __builtin_amdgcn_sched_barrier(0);
@@ -1639,28 +1639,74 @@ hipError_t launch_convt_rows32(const CRArgs& a, hipStream_t st) {
 
 // ============================================================================ C = 1 rows
 // The first Conv2D(16, 5, relu, same) + MaxPooling2D(2) (VAE/manual_scan_3layers.py:187-188)
-// on W = 128 one-channel images, as a row sweep. As in conv_c1_mfma.hip the MFMA K index is
-// (ky, kx) with kx padded to 8: lane group kg's 8 K-elements are one 8-element run of input
-// row y - 2 + kg, so B(r) = rows r .. r + 3 and output row y = A0 x B(y - 2) + A1 x B'(y + 2)
-// (A0: kernel rows 0-3, A1: row 4 in lane group 0; B' = B with lane groups 1-3 zeroed).
-// Lane m of wave w owns output columns x = 32 w + 2 m + cb (cb = 0, 1): the 2 x 2 pool of
-// pooled pixel 16 w + m is in the lane's own four accumulators (rows 2p, 2p + 1 x cb), so a
-// step (pooled row p) is 8 MFMAs per wave, no cross-lane exchange, 8-byte stores of whole
-// 512-byte pixel runs per wave. conv_c1_mfma tiles 32 x 32 with a halo and re-read the
-// input 3.3x (PMC); here every row is read once.
-//  * a staged row holds elements x = -8 .. W + 5 (zero outside the image) twice, as 32-bit
-//    words as loaded (copy 0) and shifted by one element (copy 1), so every run starts on
-//    a word of one copy: a B fragment is 4 word reads (the run of column cb comes from
-//    copy cb);
+// on W = 128 one-channel images, as a row sweep. Lane m of wave w owns pooled pixel
+// p = 16 w + m, that is output columns x = 2p + cb (cb = 0, 1), which read input columns
+// 2p - 2 .. 2p + 2 and 2p - 1 .. 2p + 3: together a six-column window from the even column
+// 2p - 2, three whole words of the staged row. The column parity is in the weights, not the
+// data: 5 kernel rows x 6 window columns = 30 of the 32 K slots of ONE 16x16x32 MFMA, and both
+// parities of an output row share one B fragment. K-slot map (lane group g, slot j = 0 .. 7, A
+// and B alike; c1_afrag / c1_bword below, restated in tests/test_conv1_pack_mapping.py):
+//    j < 6           kernel row g, window column j
+//    j = 6, 7, g < 3 kernel row 4, window column 2g + j - 6
+//    j = 6, 7, g = 3 weight zero; the lane reads a word that is always zero
+// A[cb] holds w[ch][ky][kx] at window column kx + cb (zero at the column the parity does not
+// reach), so output row y = 2p' + dy is acc[dy][cb] = A[cb] x B(y) + bias: 4 MFMAs per wave and
+// step (pooled row p'), all 25 taps each, the 2 x 2 pool in the lane's own four accumulators,
+// no cross-lane exchange, 8-byte stores of whole 512-byte pixel runs per wave. conv_c1_mfma
+// tiles 32 x 32 with a halo and re-read the input 3.3x (PMC); here every row is read once.
+//  * a staged row holds elements x = -8 .. W + 5 (zero outside the image) once, as 32-bit words
+//    as loaded: x = 0 is word 4, the window of pixel p words p + 3 .. p + 5. The B fragment of
+//    output row y (rows y - 2 .. y + 2 at positions pos .. pos + 4) is four ds_read_b32 per
+//    lane (m, g): words p + 3, p + 4, p + 5 of row pos + g and word p + 3 + g of row pos + 4
+//    (g = 3: the zero word). Rows are C1ROW = 80 = 16 (mod 32) words apart: the two rows of a
+//    half-wave read disjoint banks, row pos + 4's overlapping reads are identical words
+//    (broadcast), and the zero word (word 72 of row pos + 3 or pos + 4, a pad no DMA writes;
+//    the row by the wave's parity) sits in the 16 banks lane group 2 leaves free: every read
+//    is conflict-free at every ring position (tools/lds_banks.py);
 //  * the rows are one stream per workgroup: position il (H + 4) + r + 2 holds row r of the
 //    workgroup's image il (two zero rows above and below each image), step g = il (H/2 + 2)
 //    + p reads positions 2g .. 2g + 5 (p >= H/2: bubbles); LDS-DMA 5 steps ahead into a
-//    16-row ring (waited for two steps later), copy 1 built one step ahead of use.
-constexpr int C1W = 128;       // image width
-constexpr int C1CW = 72;       // words per copy (elements x = -8 .. W + 5, even count)
-constexpr int C1ROW = 2 * C1CW;  // words per staged row (copy 0, copy 1): 144 = 16 (mod 32)
+//    16-row ring (waited for two steps later).
+// Finite inputs are the contract. A zero weight multiplies window column 5 (cb = 0) or 0
+// (cb = 1), and row pos + 4's columns outside the parity's five: an Inf or NaN pixel there
+// reaches the other parity's accumulator of the same pool window (0 x Inf = NaN), where a
+// per-tap sum would not see it.
+constexpr int C1W = 128;   // image width
+constexpr int C1ROW = 80;  // words per staged row: elements x = -8 .. W + 5 in words 0 .. 70
+constexpr int C1ZW = 72;   // a word of the row's tail pad (words 71 .. 79: never written)
 constexpr int C1RING = 16;
 constexpr int C1LDS = C1RING * C1ROW * 4;
+
+// A fragment of column parity cb for lane (channel m, lane group g); Wg: [16][5][5]
+template <typename T>
+__device__ __forceinline__ uint4 c1_afrag(const T* __restrict__ Wg, int m, int g, int cb) {
+  uint32_t q[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    float v[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int j = 2 * i + h;
+      const int ky = j < 6 ? g : 4, c = (j < 6 ? j : 2 * g + j - 6) - cb;
+      v[h] = (j < 6 || g < 3) && c >= 0 && c <= 4 ? (float)Wg[(m * 5 + ky) * 5 + c] : 0.f;
+    }
+    q[i] = pack2<T>(v[0], v[1]);
+  }
+  return uint4{q[0], q[1], q[2], q[3]};
+}
+// The fourth word of lane (pixel p of pixel block w, lane group g)'s B fragment is word
+// c1_k4word of the row c1_k4row positions below the fragment's first: kernel row 4's columns
+// 2g, 2g + 1, or the zero word
+__device__ __forceinline__ int c1_k4row(int w, int g) { return g < 3 ? 4 : 3 + (w & 1); }
+__device__ __forceinline__ int c1_k4word(int p, int g) { return g < 3 ? p + 3 + g : C1ZW; }
+// (volatile: four separate ds_read_b32; paired into ds_read2_b32 they cost more LDS cycles)
+typedef __attribute__((address_space(3))) const volatile uint32_t c1_lds_u32;
+__device__ __forceinline__ uint4 c1_bfrag(const uint32_t* run, const uint32_t* k4) {
+  c1_lds_u32* r = (c1_lds_u32*)run;
+  c1_lds_u32* r4 = (c1_lds_u32*)k4;
+  const uint32_t a = r[0], b = r[1], c = r[2], d = r4[0];
+  return uint4{a, b, c, d};
+}
 
 template <typename T>
 __global__ __launch_bounds__(256) void conv1_rows_pool_kernel(CRArgs a) {
@@ -1675,30 +1721,13 @@ __global__ __launch_bounds__(256) void conv1_rows_pool_kernel(CRArgs a) {
   const int S = nimg * SPI;
 
   for (int e = tid; e < C1RING * C1ROW; e += 256) ring[e] = 0u;
-  // A operand: lane (m, kg) = channel m, K = (kernel row kg, kx 0..7) / (row 4 in group 0)
-  uint4 w0, w1;
-  {
-    const T* __restrict__ Wg = reinterpret_cast<const T*>(a.w);
-    uint32_t q0[4], q1[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float v[4];
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int kx = 2 * i + h;
-        v[2 * h] = kx < 5 ? (float)Wg[(m * 5 + kg) * 5 + kx] : 0.f;
-        v[2 * h + 1] = kx < 5 && kg == 0 ? (float)Wg[(m * 5 + 4) * 5 + kx] : 0.f;
-      }
-      q0[i] = pack2<T>(v[0], v[2]);
-      q1[i] = pack2<T>(v[1], v[3]);
-    }
-    w0 = uint4{q0[0], q0[1], q0[2], q0[3]};
-    w1 = uint4{q1[0], q1[1], q1[2], q1[3]};
-  }
+  // A operands: lane (m, kg) = channel m, one fragment per column parity
+  const uint4 w0 = c1_afrag<T>(reinterpret_cast<const T*>(a.w), m, kg, 0);
+  const uint4 w1 = c1_afrag<T>(reinterpret_cast<const T*>(a.w), m, kg, 1);
   const f32x4 bias = f32x4{a.b[4 * kg], a.b[4 * kg + 1], a.b[4 * kg + 2], a.b[4 * kg + 3]};
 
   // ring refill (wave 0): positions pp, pp + 1 by LDS-DMA, 16 B (8 elements) per lane from
-  // lanes 0-15, into copy 0 words 4 .. 67 (x = 0 .. W - 1); returns the DMAs issued
+  // lanes 0-15, into words 4 .. 67 (x = 0 .. W - 1); returns the DMAs issued
   const T* __restrict__ X = reinterpret_cast<const T*>(a.x);
   auto stage = [&](int pp) -> int {
     if (wv != 0) return 0;
@@ -1718,50 +1747,33 @@ __global__ __launch_bounds__(256) void conv1_rows_pool_kernel(CRArgs a) {
     }
     return nd;
   };
-  // copy 1 of positions pp, pp + 1: word i = elements (2i + 1, 2i + 2) of copy 0
-  auto shift = [&](int pp) {
-    if (tid < 2 * C1CW) {
-      const int j = tid / C1CW, i = tid - j * C1CW;
-      uint32_t* row = ring + ((pp + j) & (C1RING - 1)) * C1ROW;
-      const uint32_t lo = row[i], hi = row[i + 1];  // i = 71 reads copy 1 word 0: unused
-      row[C1CW + i] = __builtin_amdgcn_alignbit(hi, lo, 16);
-    }
-  };
   __syncthreads();  // ring zeroed
   for (int pp = 0; pp < 10; pp += 2) stage(pp);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   lds_barrier();
-  shift(0); shift(2); shift(4);
-  lds_barrier();
 
-  // B fragment of position pos (rows pos .. pos + 3 in lane groups 0..3), column block cb:
-  // words 16 w + m + 3 .. + 6 of copy cb of row pos + kg
+  // B fragment of the output row whose five input rows are at positions pos .. pos + 4
   const int wbase = 16 * wv + m + 3;
-  auto bfrag = [&](int pos, int cb) -> uint4 {
-    const uint32_t* row = ring + ((pos + kg) & (C1RING - 1)) * C1ROW + cb * C1CW + wbase;
-    return uint4{row[0], row[1], row[2], row[3]};
+  const int k4r = c1_k4row(wv, kg), k4w = c1_k4word(16 * wv + m, kg);
+  auto bfrag = [&](int pos) -> uint4 {
+    return c1_bfrag(ring + ((pos + kg) & (C1RING - 1)) * C1ROW + wbase,
+                    ring + ((pos + k4r) & (C1RING - 1)) * C1ROW + k4w);
   };
   T* __restrict__ O = reinterpret_cast<T*>(a.out);
   const int PW = C1W / 2, PH = H / 2;
   for (int g = 0; g < S; ++g) {
     // positions 2g + 10, 2g + 11 into the ring (their slots held 2g - 6, 2g - 5: done)
     const int nd = stage(2 * g + 10);
-    shift(2 * g + 6);  // copy 1 for step g + 1 (positions landed at the end of step g - 1)
     const int il = g / SPI, p = g - il * SPI;
     if (p < PH) {
       const int pb = 2 * g;  // position of input row 2p - 2
+      // output rows y = 2p + dy: both fragments before the first MFMA
+      const uint4 b0 = bfrag(pb), b1 = bfrag(pb + 1);
       f32x4 acc[2][2];
-#pragma unroll
-      for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb) {
-          // output row y = 2p + dy: B(y - 2) at position pb + dy, B'(y + 2) at pb + dy + 4
-          const uint4 b = bfrag(pb + dy, cb);
-          uint4 b4 = bfrag(pb + dy + 4, cb);
-          if (kg != 0) b4 = uint4{0u, 0u, 0u, 0u};
-          acc[dy][cb] = mfma<T>(w0, b, bias);
-          acc[dy][cb] = mfma<T>(w1, b4, acc[dy][cb]);
-        }
+      acc[0][0] = mfma<T>(w0, b0, bias);
+      acc[0][1] = mfma<T>(w1, b0, bias);
+      acc[1][0] = mfma<T>(w0, b1, bias);
+      acc[1][1] = mfma<T>(w1, b1, bias);
       float v[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i)
@@ -1771,7 +1783,7 @@ __global__ __launch_bounds__(256) void conv1_rows_pool_kernel(CRArgs a) {
       *reinterpret_cast<uint2*>(O + ((n * PH + p) * PW + 16 * wv + m) * 16 + 4 * kg) =
           uint2{pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3])};
     }
-    // wave 0: the DMAs of step g - 1 (positions 2g + 8, 2g + 9, shifted at step g + 1) must
+    // wave 0: the DMAs of step g - 1 (positions 2g + 8, 2g + 9, first read at step g + 2) must
     // land before the barrier; this step's DMAs and its store are the youngest vector-memory
     // ops, so wait for all but those. The other waves issue only stores: no wait.
     if (wv == 0) {
@@ -1812,8 +1824,12 @@ hipError_t launch_conv1_rows(const CRArgs& a, hipStream_t st) {
 // HBM. The conv2 part is conv_rows_pool_kernel<T, 16, 32, 64> step for step; instead of an
 // LDS-DMA of its input rows, step s computes the two conv2 input rows of step s + 2 with
 // the conv1 row sweep (conv1_rows_pool_kernel: waves 0-3 the first row, 4-7 the second,
-// 16 pooled pixels each) from a 32-row stream of the images' rows (4 per step: H + 4 =
-// 4 (H/4 + 1) positions per image), LDS-DMA 8 steps ahead, copy 1 built 4 steps later.
+// 16 pooled pixels each: 4 MFMAs per wave on two gathered B fragments, the same A and B
+// operands as conv1_rows_pool_kernel's for every accumulator, so the two paths agree bit for
+// bit) from a 32-row stream of the images' rows (4 per step: H + 4 = 4 (H/4 + 1) positions per
+// image), LDS-DMA 8 steps ahead. As there, finite inputs are the contract: a zero weight
+// multiplies the window's column of the other parity, so an Inf or NaN pixel reaches both
+// column parities of its pool window.
 struct E2Args {
   const void* x;    // [N][H][128] (C = 1)
   const void* w1;   // conv1 GEMM weights [16][5][5]
@@ -1824,31 +1840,14 @@ struct E2Args {
   int N, H;
 };
 
-constexpr int E2R1 = 32;  // conv1 input ring rows (positions)
-// Staged image rows: SPECENH_ENC2_COPIES element-shifted copies of C1CW words each. With 2
-// (copy c = the row shifted by c elements) a lane's 8-element B run starts on a word, so
-// it is read as two ds_read2_b32 (16 LDS cycles per fragment); with 4 (c = 0 .. 3) every
-// run starts on an even word and is read as two ds_read_b64 (8 cycles with their 2-way
-// conflicts: tools-free brute force over copy / row strides found no conflict-free even
-// layout). The conv1 B fragments are 8 of each step's 14 LDS reads per wave.
-#ifndef SPECENH_ENC2_COPIES
-#define SPECENH_ENC2_COPIES 4
-#endif
-constexpr int E2NC = SPECENH_ENC2_COPIES;
-// copy c at word E2CB(c) of a staged row. A half-wave's b64 reads cover copies (cb, cb + 2)
-// at words w .. w + 17 of one and w + 2 .. w + 19 of the other, for two ring rows: with
-// E2CB(cb) - E2CB(cb + 2) = 14 (mod 64) and a row stride of 32 (mod 64) those are 64
-// distinct banks (conflict-free; the plain 72-word stride was 2-way).
-__host__ __device__ constexpr int E2CB(int c) {
-  return E2NC == 4 ? (c == 0 ? 0 : c == 1 ? 72 : c == 2 ? 178 : 250) : c * C1CW;
-}
-constexpr int E2ROW = E2NC == 4 ? 352 : 2 * C1CW;  // words per staged row
-constexpr int E2RROWS = E2R1 + 2;                  // ring + two zero rows (parities)
+// conv1 input ring rows (positions), each staged once as in conv1_rows_pool_kernel (C1ROW
+// words; the zero word of a B fragment is a row's own tail pad, so the ring needs no zero row)
+constexpr int E2R1 = 32;
 #ifndef SPECENH_ENC2_STAGGER
 #define SPECENH_ENC2_STAGGER 0
 #endif
 
-constexpr int E2LDS = RC<16, 32, 64>::LDS + E2RROWS * E2ROW * 4 + 48 * 4;  // rings + biases
+constexpr int E2LDS = RC<16, 32, 64>::LDS + E2R1 * C1ROW * 4 + 48 * 4;  // rings + biases
 // Schedule 1's pooled-row tiles: a step's pooled row (32 pixels x 32 channels, 2 KB contiguous
 // in the NHWC output), double-buffered behind the rings and the biases. Wave (wx, nb), lane
 // (m, kg) writes the 8 bytes of channels 16 nb + 4 kg .. + 3 of pixel p = (16 wx + m) / 2 (8-byte
@@ -1893,14 +1892,14 @@ __device__ __forceinline__ uint32_t max_s16x2(uint32_t x, uint32_t y) {
 //    advanced by adds (one per step, the jump to the workgroup's next image at a boundary); the
 //    counters and the wave-uniform tests of step s + 1 are folded into one flag word under
 //    step s's MFMAs; the pooled row goes to an LDS tile (e2_tile_write) and leaves one step
-//    later as two 1 KB whole-line stores by waves 6 and 7 (the ones with no DMA and no part of
-//    the copy shift), so no wave's step opens with a store and the DMA waves' vmcnt ledger
-//    counts DMAs only; conv2's pool and ReLU run on packed 16-bit pairs, in one block with the
-//    tile write, the bookkeeping and conv1's fragment reads; the bubble's and the image top's
-//    F fragments are zeroed by address select. The order pool, conv1, conv2 is schedule 0's,
-//    and the copy shift keeps its exec-mask branch. Every accumulator keeps its order of MFMAs
-//    and every value its roundings: for finite accumulators (and infinities) bitwise equal to
-//    0; a NaN accumulator, which schedule 0's fmaxf drops, can reach the output (max_s16x2).
+//    later as two 1 KB whole-line stores by waves 6 and 7 (two of the waves with no DMA), so
+//    no wave's step opens with a store and the DMA waves' vmcnt ledger counts DMAs only;
+//    conv2's pool and ReLU run on packed 16-bit pairs, in one block with the tile write, the
+//    bookkeeping and conv1's fragment reads (both B fragments at the top of the block); the
+//    bubble's and the image top's F fragments are zeroed by address select. The order pool,
+//    conv1, conv2 is schedule 0's. Every accumulator keeps its order of MFMAs and every value
+//    its roundings: for finite accumulators (and infinities) bitwise equal to 0; a NaN
+//    accumulator, which schedule 0's fmaxf drops, can reach the output (max_s16x2).
 //    (A hand-ordered block with fragments read further ahead did not fit 128 VGPRs: DESIGN.md
 //    section 7.7.)
 template <typename T, int WPE, int SCHED = 0>
@@ -1922,11 +1921,11 @@ void enc2_rows_kernel(E2Args a) {
   const int nimg = ((int)a.N - (int)blockIdx.x + G - 1) / G;
   const int S = nimg * SPI + 1;
 
-  for (int e = tid; e < (C::LDS + E2RROWS * E2ROW * 4) / 16; e += 512)
+  for (int e = tid; e < (C::LDS + E2R1 * C1ROW * 4) / 16; e += 512)
     reinterpret_cast<uint4*>(lds)[e] = uint4{0u, 0u, 0u, 0u};
   // both layers' biases in LDS (read where used: as resident f32x4s they cost the 8 VGPRs
   // that made the 4-waves-per-SIMD build spill)
-  float* const btab = reinterpret_cast<float*>(lds + C::LDS + E2RROWS * E2ROW * 4);
+  float* const btab = reinterpret_cast<float*>(lds + C::LDS + E2R1 * C1ROW * 4);
   if (tid < 16) btab[tid] = a.b1[tid];
   else if (tid < 48) btab[tid] = a.b2[tid - 16];
   auto bias2_ld = [&]() { return *reinterpret_cast<const f32x4*>(btab + 16 + 16 * nb + 4 * kg); };
@@ -1953,41 +1952,23 @@ void enc2_rows_kernel(E2Args a) {
   const int fo = (x0 + m + 4) * 32 + 16 * (kg & 1);
   const int foff = fo + (kg >> 1) * C::ROWB, foffw = fo - (kg >> 1) * 7 * C::ROWB;
 
-  // ---- conv1: A fragments (kernel rows 0-3 / row 4 in lane group 0) ----
-  uint4 v0, v1;
-  {
-    const T* __restrict__ W1 = reinterpret_cast<const T*>(a.w1);
-    uint32_t q0[4], q1[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float v[4];
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int kx = 2 * i + h;
-        v[2 * h] = kx < 5 ? (float)W1[(m * 5 + kg) * 5 + kx] : 0.f;
-        v[2 * h + 1] = kx < 5 && kg == 0 ? (float)W1[(m * 5 + 4) * 5 + kx] : 0.f;
-      }
-      q0[i] = pack2<T>(v[0], v[2]);
-      q1[i] = pack2<T>(v[1], v[3]);
-    }
-    v0 = uint4{q0[0], q0[1], q0[2], q0[3]};
-    v1 = uint4{q1[0], q1[1], q1[2], q1[3]};
-  }
+  // ---- conv1: A fragments of column parity 0 / 1 (conv1_rows_pool_kernel's) ----
+  const uint4 v0 = c1_afrag<T>(reinterpret_cast<const T*>(a.w1), m, kg, 0);
+  const uint4 v1 = c1_afrag<T>(reinterpret_cast<const T*>(a.w1), m, kg, 1);
   resident_loads_landed();
   const int w1x = wv & 3, jr = wv >> 2;  // conv1 pixel block, conv2 input row of the pair
-  const int wbase = 16 * w1x + m + 3;
-  // 4 copies: the run of pooled pixel p = 16 w1x + m at column parity cb starts at element
-  // 2 p + cb + 6 of copy 0; copy c = that element mod 4 holds it at the even word w4
-  const int p1 = 16 * w1x + m;
-  const int c4hi = 2 * ((p1 + 3) & 1), w4 = p1 + 3 - ((p1 + 3) & 1);
-  const int cbase0 = E2CB(c4hi) + w4, cbase1 = E2CB(1 + c4hi) + w4;  // column parity 0 / 1
+  // this lane's words of a B fragment at position pos: words p + 3 .. p + 5 of ring row
+  // pos + kg and the fourth word, as byte offsets from ring row pos (two lane registers; the
+  // wrap past the ring's end is an unsigned min: see bfrag)
+  const uint32_t boA = (kg * C1ROW + 16 * w1x + m + 3) * 4;
+  const uint32_t boK = (c1_k4row(w1x, kg) * C1ROW + c1_k4word(16 * w1x + m, kg)) * 4;
 
   // image-row stream: position pp = il (H1 + 4) + y + 2; waves 0-3 move positions pp + wv.
   // The loop keeps (image, row) of its positions and steps as scalar counters advanced per
   // step (a run-time division per use had cost ~25 SALU + a VALU reciprocal each).
   const T* __restrict__ X = reinterpret_cast<const T*>(a.x);
   auto stage1_at = [&](int pos, int il, int y) -> int {  // position pos = il PPI + y + 2
-    uint32_t* dst = ring1 + (pos & (E2R1 - 1)) * E2ROW + 4;
+    uint32_t* dst = ring1 + (pos & (E2R1 - 1)) * C1ROW + 4;
     if (il < nimg && y >= 0 && y < H1) {
       const long long n = (long long)blockIdx.x + (long long)il * G;
       // wave-uniform row base + 16 B per lane (SGPR base, no 64-bit lane address to keep)
@@ -2006,42 +1987,26 @@ void enc2_rows_kernel(E2Args a) {
     const int il = pos / PPI;
     return stage1_at(pos, il, pos - il * PPI - 2);
   };
-  auto shift1 = [&](int pp) {  // copies 1 .. E2NC - 1 of positions pp .. pp + 3
-    constexpr int NW = E2NC == 4 ? C1CW - 2 : C1CW;  // (copy 0 words read: i .. i + 2)
-    if (tid < 4 * NW) {
-      const int j = tid / NW, i = tid - j * NW;
-      uint32_t* row = ring1 + ((pp + j) & (E2R1 - 1)) * E2ROW;
-      const uint32_t r0 = row[i], r1 = row[i + 1];
-      row[E2CB(1) + i] = __builtin_amdgcn_alignbit(r1, r0, 16);
-      if constexpr (E2NC == 4) {
-        const uint32_t r2 = row[i + 2];
-        row[E2CB(2) + i] = r1;
-        row[E2CB(3) + i] = __builtin_amdgcn_alignbit(r2, r1, 16);
-      }
+  // B fragment of the conv1 output row whose input rows are at positions pos .. pos + 4
+  // (pos is wave-uniform: its ring row is a scalar, and a lane's row 0 .. 4 further on wraps
+  // at most once: offset o < 2 RB is o mod RB = min(o, o - RB) in unsigned arithmetic)
+  auto bfrag = [&](int pos) -> uint4 {
+    constexpr uint32_t RB = E2R1 * C1ROW * 4;
+    const uint32_t sb = (uint32_t)(pos & (E2R1 - 1)) * (C1ROW * 4);
+    const uint32_t oA = sb + boA, oK = sb + boK;
+    const unsigned char* r1b = reinterpret_cast<const unsigned char*>(ring1);
+    return c1_bfrag(reinterpret_cast<const uint32_t*>(r1b + min(oA, oA - RB)),
+                    reinterpret_cast<const uint32_t*>(r1b + min(oK, oK - RB)));
+  };
+  // the four accumulators of a pool window (rows dy of the two fragments x column parities),
+  // bias + all 25 taps in one MFMA each, into the running max v (starts at 0: ReLU folded)
+  auto c1_window = [&](float (&v)[4], const uint4& bA, const uint4& bB, const f32x4& bias1) {
+#pragma unroll
+    for (int pr = 0; pr < 4; ++pr) {
+      const f32x4 acc1 = mfma<T>(pr & 1 ? v1 : v0, pr >> 1 ? bB : bA, bias1);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) v[i] = fmaxf(v[i], acc1[i]);
     }
-  };
-  auto run_at = [&](const uint32_t* row, int cb) -> uint4 {  // row: staged row start
-    if constexpr (E2NC == 4) {
-      // volatile: two separate ds_read_b64 (2 LDS cycles each); the compiler otherwise pairs
-      // reads into ds_read2_b64, which costs 8
-      typedef __attribute__((address_space(3))) const volatile unsigned long long lds_u64;
-      const lds_u64* r = (const lds_u64*)(row + (cb ? cbase1 : cbase0));
-      const unsigned long long lo = r[0], hi = r[1];
-      return uint4{(uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32)};
-    } else {
-      const uint32_t* r = row + cb * C1CW + wbase;
-      return uint4{r[0], r[1], r[2], r[3]};
-    }
-  };
-  auto bfrag = [&](int pos, int cb) -> uint4 {
-    return run_at(ring1 + ((pos + kg) & (E2R1 - 1)) * E2ROW, cb);
-  };
-  // B' (kernel row 4 only): lane group 0 reads row pos, groups 1-3 the zero row past the ring
-  // (an address select instead of zeroing 4 data registers)
-  // (two zero rows: the one an odd number of rows from pos, so its banks miss lane group 0's)
-  auto bfrag4 = [&](int pos, int cb) -> uint4 {
-    const uint32_t* zrow = ring1 + (E2NC == 4 ? E2R1 + 1 - (pos & 1) : E2R1) * E2ROW;
-    return run_at(kg == 0 ? ring1 + (pos & (E2R1 - 1)) * E2ROW : zrow, cb);
   };
   // conv2 input row 2 q2 + jr of conv2 step g2 (image g2 / SPI) into its ring slot: pooled
   // pixels 16 w1x + m, channels 4 kg .. 4 kg + 3 (zero rows outside the image)
@@ -2052,18 +2017,8 @@ void enc2_rows_kernel(E2Args a) {
     // ring holds and replaced by zeros
     const int pb = 4 * g2 + 2 * jr;  // position of image row 2r - 2
     float v[4] = {0.f, 0.f, 0.f, 0.f};
-    const f32x4 bias1 = *reinterpret_cast<const f32x4*>(btab + 4 * kg);
-#pragma unroll
-    for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-      for (int cb = 0; cb < 2; ++cb) {
-        const uint4 b = bfrag(pb + dy, cb);
-        const uint4 b4 = bfrag4(pb + dy + 4, cb);
-        f32x4 acc1 = mfma<T>(v0, b, bias1);
-        acc1 = mfma<T>(v1, b4, acc1);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = fmaxf(v[i], acc1[i]);  // (>= 0: relu folded)
-      }
+    const uint4 bA = bfrag(pb), bB = bfrag(pb + 1);
+    c1_window(v, bA, bB, *reinterpret_cast<const f32x4*>(btab + 4 * kg));
     const bool real = il < nimg && r < H;
     const uint2 pk = real ? uint2{pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3])} : uint2{0u, 0u};
     *reinterpret_cast<uint2*>(ring + ((2 * g2 + jr) & 7) * C::ROWB + (16 * w1x + m + 2) * 32 +
@@ -2073,8 +2028,6 @@ void enc2_rows_kernel(E2Args a) {
   __syncthreads();  // rings zeroed
   for (int pp = 0; pp < 32; pp += 4) stage1(pp);  // positions 0 .. 31 (steps -8 .. -1)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  lds_barrier();
-  for (int pp = 0; pp < 16; pp += 4) shift1(pp);
   lds_barrier();
   produce(0, 0, 0);
   produce(1, 1 / SPI, 1 % SPI);
@@ -2180,18 +2133,9 @@ void enc2_rows_kernel(E2Args a) {
       asm volatile("" : "+s"(fl), "+s"(dreal), "+s"(ob), "+s"(obp), "+s"(xs));
     };
     auto ld16 = [](const unsigned char* p) { return *reinterpret_cast<const uint4*>(p); };
-    // one (dy, cb) pair of conv1: the two fragments, then bias + the 25 taps in two MFMAs
-    struct Pair { uint4 b, b4; };
-    auto c1_read = [&](int pb, int pr) {
-      return Pair{bfrag(pb + (pr >> 1), pr & 1), bfrag4(pb + (pr >> 1) + 4, pr & 1)};
-    };
-    // running max of the pairs' outputs, ReLU folded (starts at 0), as schedule 0's (it compiles
-    // to two v_max3_f32 per value: on packed pairs it took as many instructions, with the
+    // (conv1's running max of the window's four outputs, c1_window, is schedule 0's: it compiles
+    // to two v_max3_f32 per value; on packed pairs it took as many instructions, with the
     // converts, and more registers)
-    auto c1_max = [&](float (&v)[4], const f32x4& acc1) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) v[i] = fmaxf(v[i], acc1[i]);
-    };
 
     auto step1 = [&](auto ic, const int s) {
       constexpr int I = decltype(ic)::value % 3, P = decltype(ic)::value & 1;
@@ -2202,11 +2146,10 @@ void enc2_rows_kernel(E2Args a) {
       // (1) the pooled row that step s - 1 left in its tile: two whole-line stores
       if (wv >= 6 && (flc & F_HELD)) store_tile(obp, (P ^ 1) * E2TILE);
       CR_MARK(0);
-      // (2) image rows 8 steps ahead, copies 1 .. 3 of positions 4s + 16 .. 4s + 19 (as
-      // schedule 0)
+      // (2) image rows 8 steps ahead (as schedule 0)
       int nd = 0;
       if (wv < 4) {
-        uint32_t* dst = ring1 + ((4 * s + wv) & (E2R1 - 1)) * E2ROW + 4;
+        uint32_t* dst = ring1 + ((4 * s + wv) & (E2R1 - 1)) * C1ROW + 4;
         if (dreal) {
           if (lane < 16) lds_dma16_s(xs, 16u * lane, dst);
           nd = 1;
@@ -2216,15 +2159,16 @@ void enc2_rows_kernel(E2Args a) {
           if (lane < 16) *reinterpret_cast<uint4*>(dst + 4 * lane) = uint4{(uint32_t)z, (uint32_t)z, (uint32_t)z, (uint32_t)z};
         }
       }
-      shift1(4 * s + 16);
       CR_MARK(1);
-      // (3) the arithmetic. conv2's input rows (2s, 2s + 1: ring slots rs, rs + 1, rs even)
-      // landed before the barrier: their fragments first. The F fragment of the bubble's
+      // (3) the arithmetic, opened by conv1's two B fragments (the window rows of step s + 2:
+      // eight ds_read_b32 in flight at once). conv2's input rows (2s, 2s + 1: ring slots rs,
+      // rs + 1, rs even) landed before the barrier. The F fragment of the bubble's
       // second row and F(-1) off an image's top are read from the ring's first 16 bytes, a
       // halo no step writes (zeros), by address select; F(-1) only in lane groups 2, 3.
       const int rs = (2 * s) & 7;
       const unsigned char* rb = ring + rs * C::ROWB;
       const int pb = 4 * (s + 2) + 2 * jr;
+      const uint4 bA = bfrag(pb), bB = bfrag(pb + 1);
       // (slot 7 pairs with slot 0: foffw = foff - 8 ROWB in lane groups 2, 3)
       const int fo1 = (flc & F_CBUB) ? 0 : (rs + 1) * C::ROWB + (rs == 6 && kg >= 2 ? foff - 8 * C::ROWB : foff);
       const int foT = (flc & F_CTOP) && kg >= 2 ? (rs - 1) * C::ROWB + foff : 0;  // (fo = foff - ROWB there)
@@ -2233,9 +2177,6 @@ void enc2_rows_kernel(E2Args a) {
         const int d = w < 10 ? j + 2 - w % 5 : w == 10 ? j + 2 : w == 11 ? j : j - 2;
         acc[slot(d)] = mfma<T>(wf[w], b, acc[slot(d)]);
       };
-      const f32x4 bias1 = *reinterpret_cast<const f32x4*>(btab + 4 * kg);
-      auto c1a = [&](const Pair& f) { return mfma<T>(v0, f.b, bias1); };
-      auto c1b = [&](const Pair& f, const f32x4& a1) { return mfma<T>(v1, f.b4, a1); };
       {  // pair s - 2: pool on the packed pairs (rows in lane, columns across the lane pair
          // m, m ^ 1, ReLU), reset, into the tile: unconditionally, a tile no flag marks is
          // never stored
@@ -2251,11 +2192,7 @@ void enc2_rows_kernel(E2Args a) {
             uint2{max_s16x2(max_s16x2(p0, nbr(p0)), 0u), max_s16x2(max_s16x2(p1, nbr(p1)), 0u)};
       }
       next();
-#pragma unroll
-      for (int pr = 0; pr < 4; ++pr) {
-        const Pair f = c1_read(pb, pr);
-        c1_max(v, c1b(f, c1a(f)));
-      }
+      c1_window(v, bA, bB, *reinterpret_cast<const f32x4*>(btab + 4 * kg));
       CR_MARK(2);
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
@@ -2336,11 +2273,9 @@ void enc2_rows_kernel(E2Args a) {
     }
     CR_MARK(0);
     // image rows 8 steps ahead (positions 4s + 32 .. 4s + 35: slots of 4s .. 4s + 3, whose
-    // last readers were this step's predecessors), copy 1 of positions 4s + 16 .. 4s + 19
-    // (landed: DMA of step s - 4, waited at the end of step s - 1), conv2 input rows of
-    // step s + 2 (positions 4s + 8 .. 4s + 15)
+    // last readers were this step's predecessors), conv2 input rows of step s + 2 (positions
+    // 4s + 8 .. 4s + 15: DMAs of steps s - 6 and s - 5, waited at the end of step s - 2)
     const int nd = wv < 4 ? stage1_at(4 * s + 32 + wv, ilD, rD - 2) : 0;
-    shift1(4 * s + 16);
     CR_MARK(1);
     // this step's conv2 rows, unconditionally: past an image they are the zero rows the
     // conv1 stage stored (adding nothing)
@@ -2393,7 +2328,7 @@ void enc2_rows_kernel(E2Args a) {
       conv2_rows();
     }
     CR_MARK(3);
-    // the DMA of step s - 3 (copy-1 shifted at step s + 1) must have landed: wait for all
+    // the DMA of step s - 3 (first read by conv1 at step s + 2) must have landed: wait for all
     // but this wave's vector-memory ops of steps s - 2 .. s (each step: its store, then its
     // DMA). Only the DMA waves wait; stores alone are never waited for.
     if (wv < 4) {

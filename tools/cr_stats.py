@@ -9,9 +9,9 @@ and the barrier wait. Schedule 1 has no separate head or read segment (both run 
 block).
 With `enc2`: enc2_rows_kernel at the C5 fused-encoder launch shape (N images of H x 128), for
 each schedule (ENC2_SCHED = 0, 1): the pool + store head (schedule 1: the two storing waves'
-whole-line store), the DMA issue + the copy shift, conv1 (schedule 1: with the pool under it),
-the conv2 block, the vmcnt wait and the barrier wait; waves 0-3 (DMA, most of the shift, the
-ledger) and waves 4-7 also as two means.
+whole-line store), the DMA issue (image rows are staged once: no copy shift since the packed
+conv1), conv1 (schedule 1: with the pool under it), the conv2 block, the vmcnt wait and the
+barrier wait; waves 0-3 (DMA, the ledger) and waves 4-7 also as two means.
 A stamp is an s_memtime and two lgkmcnt waits: read the shares, not the totals. Waves 0-3 move
 the rows (LDS-DMA); wave w shares a SIMD with w + 4."""
 import ctypes
@@ -30,7 +30,7 @@ args = sys.argv[1:]
 ENC2 = bool(args) and args[0] == "enc2"
 if ENC2:
     args = args[1:]
-SEGS = ["head", "dma+shift", "conv1", "conv2", "vmcnt", "barrier"] if ENC2 else \
+SEGS = ["head", "dma", "conv1", "conv2", "vmcnt", "barrier"] if ENC2 else \
     ["head", "dma", "reads", "mfma", "vmcnt", "barrier"]
 SWITCH = "ENC2_SCHED" if ENC2 else "CONV_ROWS_SCHED"
 N = int(args[0]) if len(args) > 0 else 2048
