@@ -37,6 +37,7 @@
 #include <cstdlib>
 #include <string>
 
+#include "mma.hpp"
 #include "specenh.h"
 #include "runtime.hpp"
 #include "wave.hpp"
@@ -50,22 +51,6 @@ int launch_conv_c1_mfma(int dtype, const void* in, int N, int IH, int IW, int C,
                         int KH, int KW, int CO, const float* bias, int pad_t, int pad_l, int OH,
                         int OW, int act, void* out, int out_f32, float* logits, int pool,
                         unsigned char* argmax, const void* mask, hipStream_t st);  // conv_c1_mfma.hip
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float to_f(float x) { return x; }
-__device__ __forceinline__ float to_f(__bf16 x) { return (float)x; }
-__device__ __forceinline__ float to_f(_Float16 x) { return (float)x; }
-template <typename T>
-__device__ __forceinline__ T from_f(float x);
-template <>
-__device__ __forceinline__ float from_f<float>(float x) { return x; }
-template <>
-__device__ __forceinline__ __bf16 from_f<__bf16>(float x) { return (__bf16)x; }
-template <>
-__device__ __forceinline__ _Float16 from_f<_Float16>(float x) { return (_Float16)x; }
 
 // ------------------------------------------------------------------ geometry
 // One dense implicit GEMM (one output phase):
@@ -133,14 +118,6 @@ __device__ __forceinline__ void zero8(V8<T>& v) {
   for (int i = 0; i < (int)(sizeof(T) * 2); ++i) v.w[i] = 0u;
 }
 
-__device__ __forceinline__ uint32_t bits(float x) { return __float_as_uint(x); }
-__device__ __forceinline__ uint32_t bits(__bf16 x) {
-  return (uint32_t)__builtin_bit_cast(unsigned short, x);
-}
-__device__ __forceinline__ uint32_t bits(_Float16 x) {
-  return (uint32_t)__builtin_bit_cast(unsigned short, x);
-}
-
 // element j of a V8 (as raw bits)
 template <typename T>
 __device__ __forceinline__ uint32_t elem_bits(const V8<T>& v, int j) {
@@ -156,28 +133,6 @@ __device__ __forceinline__ void set_elem(V8<T>& v, int j, T x) {
     const uint32_t b = bits(x) << (16 * (j & 1));
     v.w[j >> 1] = (v.w[j >> 1] & (0xffff0000u >> (16 * (j & 1)))) | b;
   }
-}
-
-// Two floats rounded to T (round to nearest even) and packed into one 32-bit word, element
-// a in the low half: v_cvt_pk_bf16_f32 / two v_cvt_f16_f32 + v_pack_b32_f16 (no mask ops).
-template <typename T>
-__device__ __forceinline__ uint32_t pack2(float a, float b) {
-  if constexpr (__is_same(T, __bf16)) {
-    typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(uint32_t, b2{(__bf16)a, (__bf16)b});
-  } else {
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(uint32_t, h2{(_Float16)a, (_Float16)b});
-  }
-}
-
-// max(a, b) without the NaN-quieting canonicalisation fmaxf gets (operands are
-// accumulators: finite unless the inputs hold NaN/Inf) as v_med3_f32(a, b, +inf): a
-// builtin, not inline asm, so the compiler's hazard recognizer sees the read of an MFMA
-// result and pads the XDL-write -> VALU-read wait states (inside an asm statement it
-// does not)
-__device__ __forceinline__ float vmax(float a, float b) {
-  return __builtin_amdgcn_fmed3f(a, b, __builtin_inff());
 }
 
 // 8 GEMM-K elements k .. k+7 of one output pixel (by, bx = top-left of its window, nb =
@@ -457,23 +412,6 @@ __device__ __forceinline__ V8<T> ldw(__amdgpu_buffer_rsrc_t r, int voff, int sof
   const u32x4 a = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
   V8<T> v;
   v.w[0] = a.x; v.w[1] = a.y; v.w[2] = a.z; v.w[3] = a.w;
-  return v;
-}
-
-template <typename T>
-__device__ __forceinline__ f32x4 mfma32(const V8<T>& a, const V8<T>& b, f32x4 acc) {
-  if constexpr (__is_same(T, __bf16)) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a),
-                                                   __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
-  } else {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a),
-                                                  __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
-  }
-}
-
-__device__ __forceinline__ float apply_act(float v, int act) {
-  if (act == 1) return fmaxf(v, 0.f);
-  if (act == 2) return 1.f / (1.f + __expf(-v));
   return v;
 }
 
@@ -770,7 +708,7 @@ void conv_patch_kernel(ConvArgs a) {
 #pragma unroll
           for (int i = 0; i < MT; ++i)
 #pragma unroll
-            for (int j = 0; j < NT; ++j) acc[i][j] = mfma32<T>(wring[u][j], pv[i], acc[i][j]);
+            for (int j = 0; j < NT; ++j) acc[i][j] = mfma16x16x32<T>(wring[u][j], pv[i], acc[i][j]);
           const int col = wcol_of(min(st + PD, nsteps - 1));
 #pragma unroll
           for (int j = 0; j < NT; ++j) wring[u][j] = ldw<T>(wrs, wv[j], col * (int)sizeof(T));
@@ -789,7 +727,7 @@ void conv_patch_kernel(ConvArgs a) {
 #pragma unroll
           for (int i = 0; i < MT; ++i)
 #pragma unroll
-            for (int j = 0; j < NT; ++j) acc[i][j] = mfma32<T>(wring[u][j], pv[i], acc[i][j]);
+            for (int j = 0; j < NT; ++j) acc[i][j] = mfma16x16x32<T>(wring[u][j], pv[i], acc[i][j]);
         }
       } else if constexpr (CC == 16) {
         // ---- 16 channels: one MFMA K=32 slab = two taps (lane groups kgrp 0-1: tap 2st,
@@ -866,7 +804,7 @@ void conv_patch_kernel(ConvArgs a) {
 #pragma unroll
             for (int i = 0; i < MT; ++i)
 #pragma unroll
-              for (int j = 0; j < NT; ++j) acc[i][j] = mfma32<T>(wf[j], pv[i], acc[i][j]);
+              for (int j = 0; j < NT; ++j) acc[i][j] = mfma16x16x32<T>(wf[j], pv[i], acc[i][j]);
           }
         } else if constexpr (WL) {
           // weights from the LDS copy: no global loads (and no vmcnt waits) in the k-loop
@@ -897,7 +835,7 @@ void conv_patch_kernel(ConvArgs a) {
 #pragma unroll
             for (int i = 0; i < MT; ++i)
 #pragma unroll
-              for (int j = 0; j < NT; ++j) acc[i][j] = mfma32<T>(wf[j], pv[i], acc[i][j]);
+              for (int j = 0; j < NT; ++j) acc[i][j] = mfma16x16x32<T>(wf[j], pv[i], acc[i][j]);
           }
         } else {
         constexpr int PD = WS ? (NT == 1 ? 4 : 2) : (NT >= 3 ? 2 : (NT == 2 ? 2 : 8));
@@ -929,7 +867,7 @@ void conv_patch_kernel(ConvArgs a) {
 #pragma unroll
           for (int i = 0; i < MT; ++i)
 #pragma unroll
-            for (int j = 0; j < NT; ++j) acc[i][j] = mfma32<T>(wring[u][j], pv[i], acc[i][j]);
+            for (int j = 0; j < NT; ++j) acc[i][j] = mfma16x16x32<T>(wring[u][j], pv[i], acc[i][j]);
           if (st + PD < nsteps) wload(st + PD, wring[u]);
         }
         }  // !WL
@@ -1000,7 +938,7 @@ void conv_patch_kernel(ConvArgs a) {
               if (!aon) zero8(pv);
             }
   #pragma unroll
-            for (int j = 0; j < NT; ++j) acc[i][j] = mfma32<T>(wcur[j], pv, acc[i][j]);
+            for (int j = 0; j < NT; ++j) acc[i][j] = mfma16x16x32<T>(wcur[j], pv, acc[i][j]);
           }
         }
       }
@@ -1044,7 +982,7 @@ void conv_patch_kernel(ConvArgs a) {
             if (store && ch0 < g.CO) {
               const long long o = (((long long)n * PHo + py) * PWo + pxo) * g.CO + ch0;
               *reinterpret_cast<uint2*>(reinterpret_cast<T*>(a.out) + o) =
-                  uint2{pack2<T>(m[0], m[1]), pack2<T>(m[2], m[3])};
+                  uint2{pack2_vec<T>(m[0], m[1]), pack2_vec<T>(m[2], m[3])};
             }
           }
         }
@@ -1060,8 +998,8 @@ void conv_patch_kernel(ConvArgs a) {
           unsigned arg4 = 0;
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float v00 = to_f(from_f<T>(apply_act(acc[2 * ip][j][r] + bv[j][r], a.act)));
-            const float v10 = to_f(from_f<T>(apply_act(acc[2 * ip + 1][j][r] + bv[j][r], a.act)));
+            const float v00 = to_f(from_f<T>(act_f(acc[2 * ip][j][r] + bv[j][r], a.act)));
+            const float v10 = to_f(from_f<T>(act_f(acc[2 * ip + 1][j][r] + bv[j][r], a.act)));
             const float v01 = __shfl_xor(v00, 1);
             const float v11 = __shfl_xor(v10, 1);
             float b = v00;
@@ -1103,7 +1041,7 @@ void conv_patch_kernel(ConvArgs a) {
           V8<T> q;
           zero8(q);
 #pragma unroll
-          for (int r = 0; r < 4; ++r) set_elem(q, r, from_f<T>(apply_act(acc[i][j][r] + bv[j][r], a.act)));
+          for (int r = 0; r < 4; ++r) set_elem(q, r, from_f<T>(act_f(acc[i][j][r] + bv[j][r], a.act)));
           pk[i][j][0] = q.w[0];
           pk[i][j][1] = q.w[1];
         }
@@ -1172,7 +1110,7 @@ void conv_patch_kernel(ConvArgs a) {
               v[r] = to_f(mv) > 0.f ? v[r] : 0.f;
             }
           }
-          *reinterpret_cast<uint2*>(out + o + ch0) = uint2{pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3])};
+          *reinterpret_cast<uint2*>(out + o + ch0) = uint2{pack2_vec<T>(v[0], v[1]), pack2_vec<T>(v[2], v[3])};
         }
       }
     } else {
@@ -1197,19 +1135,19 @@ void conv_patch_kernel(ConvArgs a) {
               float x = v[r];
               if (a.logits) a.logits[o + r] = x;
               if (a.mask && !(to_f(reinterpret_cast<const T*>(a.mask)[o + r]) > 0.f)) x = 0.f;
-              x = apply_act(x, a.act);
+              x = act_f(x, a.act);
               if (a.out_f32) reinterpret_cast<float*>(a.out)[o + r] = x;
               else reinterpret_cast<T*>(a.out)[o + r] = from_f<T>(x);
             }
           } else if (a.out_f32) {
             *reinterpret_cast<float4*>(reinterpret_cast<float*>(a.out) + o) =
-                float4{apply_act(v[0], a.act), apply_act(v[1], a.act), apply_act(v[2], a.act),
-                       apply_act(v[3], a.act)};
+                float4{act_f(v[0], a.act), act_f(v[1], a.act), act_f(v[2], a.act),
+                       act_f(v[3], a.act)};
           } else {
             V8<T> pk;
             zero8(pk);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) set_elem(pk, r, from_f<T>(apply_act(v[r], a.act)));
+            for (int r = 0; r < 4; ++r) set_elem(pk, r, from_f<T>(act_f(v[r], a.act)));
             *reinterpret_cast<uint2*>(reinterpret_cast<T*>(a.out) + o) = uint2{pk.w[0], pk.w[1]};
           }
         }
@@ -1396,14 +1334,11 @@ __device__ __forceinline__ s16x4 lds_tr16(const void* p) {
       (__attribute__((address_space(3))) s16x4*)(const_cast<void*>(p)));
 }
 
+// raw-short fragments BY VALUE (mma.hpp's takes references): wgrad_trp_kernel's choice between
+// two A fragments then selects values, not addresses, as its code was built
 template <typename T>
 __device__ __forceinline__ f32x4 mfma_s16(s16x8 a, s16x8 b, f32x4 acc) {
-  if constexpr (__is_same(T, __bf16))
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a),
-                                                   __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a),
-                                                  __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
+  return mfma16x16x32<T>(a, b, acc);
 }
 
 // C1 (one input channel, the first Conv2D): the B tile is an im2col block built in LDS per tile

@@ -27,16 +27,13 @@
 #include <cstdint>
 #include <string>
 
+#include "mma.hpp"
 #include "specenh.h"
 #include "runtime.hpp"
 
 namespace specenh {
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 struct C1mArgs {
   const void* in;    // [N][IH][IW] (C == 1)
@@ -53,45 +50,6 @@ constexpr int PRS = 40;  // patch rows (32 + K - 1 <= 39), + 1 for clamped reads
 constexpr int RW = 20;   // staged row: 20 words = 40 elements (runs start at <= 32, 8 long)
 constexpr int RDW = 48;  // LDS row pitch in words: the 4 kernel-row lane groups of a
                          // fragment read sit 48 = -16 (mod 64) banks apart: conflict-free
-
-template <typename T>
-__device__ __forceinline__ float tof(T x) { return (float)x; }
-
-template <typename T>
-__device__ __forceinline__ f32x4 mfma(uint4 a, uint4 b, f32x4 c) {
-  if constexpr (__is_same(T, __bf16))
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a),
-                                                   __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a),
-                                                  __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
-template <typename T>
-__device__ __forceinline__ uint32_t pack2(float a, float b) {
-  if constexpr (__is_same(T, __bf16)) {
-    typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(uint32_t, b2{(__bf16)a, (__bf16)b});
-  } else {
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(uint32_t, h2{(_Float16)a, (_Float16)b});
-  }
-}
-
-// max(a, b) without the NaN-quieting canonicalisation fmaxf gets (operands are
-// accumulators: finite unless the inputs hold NaN/Inf) as v_med3_f32(a, b, +inf): a
-// builtin, not inline asm, so the compiler's hazard recognizer sees the read of an MFMA
-// result and pads the XDL-write -> VALU-read wait states (inside an asm statement it
-// does not)
-__device__ __forceinline__ float vmax(float a, float b) {
-  return __builtin_amdgcn_fmed3f(a, b, __builtin_inff());
-}
-
-__device__ __forceinline__ float act_f(float v, int act) {
-  if (act == SPECENH_ACT_RELU) return fmaxf(v, 0.f);
-  if (act == SPECENH_ACT_SIGMOID) return 1.f / (1.f + __expf(-v));
-  return v;
-}
 
 template <typename T, bool POOL, int PAR>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void conv_c1_mfma_kernel(C1mArgs a) {
@@ -199,7 +157,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void c
         if (s >= nks) break;  // uniform
         const int r = rw0 + i + 4 * s + g4;  // <= 38 < PRS; rows past K meet zero weights
         const uint32_t* q = (cb == PAR ? sP0 + PAR : sP1) + r * RDW + l16;
-        acc[i][cb] = mfma<T>(wf[s], uint4{q[0], q[1], q[2], q[3]}, acc[i][cb]);
+        acc[i][cb] = mfma16x16x32<T>(wf[s], uint4{q[0], q[1], q[2], q[3]}, acc[i][cb]);
       }
 
   // ---- epilogue: lane holds channels co0 + 4 g4 + r of pixels (rw0 + i, 2 l16 + cb) ----
@@ -225,10 +183,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void c
       } else {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float v00 = tof((T)act_f(acc[2 * ip][0][r] + bv[r], a.act));
-          const float v01 = tof((T)act_f(acc[2 * ip][1][r] + bv[r], a.act));
-          const float v10 = tof((T)act_f(acc[2 * ip + 1][0][r] + bv[r], a.act));
-          const float v11 = tof((T)act_f(acc[2 * ip + 1][1][r] + bv[r], a.act));
+          const float v00 = to_f((T)act_f(acc[2 * ip][0][r] + bv[r], a.act));
+          const float v01 = to_f((T)act_f(acc[2 * ip][1][r] + bv[r], a.act));
+          const float v10 = to_f((T)act_f(acc[2 * ip + 1][0][r] + bv[r], a.act));
+          const float v11 = to_f((T)act_f(acc[2 * ip + 1][1][r] + bv[r], a.act));
           float b = v00;
           unsigned q = 0;
           if (v01 > b) { b = v01; q = 1; }
@@ -240,7 +198,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void c
       }
       if (!store) continue;
       if (vec) {
-        *reinterpret_cast<uint2*>(dst) = uint2{pack2<T>(m[0], m[1]), pack2<T>(m[2], m[3])};
+        *reinterpret_cast<uint2*>(dst) = uint2{pack2_vec<T>(m[0], m[1]), pack2_vec<T>(m[2], m[3])};
         if (a.argmax) *reinterpret_cast<unsigned*>(a.argmax + o) = arg4;
       } else {
 #pragma unroll
@@ -270,17 +228,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void c
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               const T mv = __builtin_bit_cast(T, (unsigned short)(mw[r >> 1] >> (16 * (r & 1))));
-              v[r] = tof(mv) > 0.f ? v[r] : 0.f;
+              v[r] = to_f(mv) > 0.f ? v[r] : 0.f;
             }
           }
           *reinterpret_cast<uint2*>(reinterpret_cast<T*>(a.out) + o) =
-              uint2{pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3])};
+              uint2{pack2_vec<T>(v[0], v[1]), pack2_vec<T>(v[2], v[3])};
         } else {
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             if (ch0 + r >= a.CO) continue;
             float x = v[r];
-            if (mk && !(tof(mk[o + r]) > 0.f)) x = 0.f;
+            if (mk && !(to_f(mk[o + r]) > 0.f)) x = 0.f;
             reinterpret_cast<T*>(a.out)[o + r] = (T)x;
           }
         }
@@ -290,30 +248,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void c
   }  // images
 }
 
-template <typename T, bool POOL>
+template <typename T, bool POOL, int PAR>
 int launch_t(const C1mArgs& a, hipStream_t st) {
   const long long tpi = (long long)((a.OH + TILE - 1) / TILE) * ((a.OW + TILE - 1) / TILE);
-  const int cus = device_cus();
-  const bool par = a.pad_l & 1;
-  const void* fn = par ? (const void*)conv_c1_mfma_kernel<T, POOL, 1>
-                       : (const void*)conv_c1_mfma_kernel<T, POOL, 0>;
-  static int per_cu[2] = {0, 0};
-  int& pc = per_cu[POOL ? 1 : 0];
-  if (pc == 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, fn, 256, 0) != hipSuccess || pc <= 0))
-    pc = 2;
+  static ResidentSlots site;
+  long long slots = 0;
+  if (resident_slots(site, (const void*)conv_c1_mfma_kernel<T, POOL, PAR>, 256, 0, &slots) != hipSuccess)
+    return set_error(SPECENH_EHIP, "conv_c1_mfma occupancy");
   const unsigned cob = (unsigned)((a.CO + 15) / 16);
   // persistent: each workgroup keeps one tile position and walks the images; as many
   // image groups as fill the resident slots (at least one)
-  const long long groups = std::max<long long>(1, std::min<long long>(a.N, (long long)pc * cus / cob / tpi));
+  const long long groups = std::max<long long>(1, std::min<long long>(a.N, slots / cob / tpi));
   const dim3 grid((unsigned)(groups * tpi), cob);
-  if (par) SPECENH_LAUNCH((conv_c1_mfma_kernel<T, POOL, 1>), grid, dim3(256), 0, st, a);
-  else SPECENH_LAUNCH((conv_c1_mfma_kernel<T, POOL, 0>), grid, dim3(256), 0, st, a);
+  SPECENH_LAUNCH((conv_c1_mfma_kernel<T, POOL, PAR>), grid, dim3(256), 0, st, a);
   return hipGetLastError() == hipSuccess ? 1 : set_error(SPECENH_EHIP, "conv_c1_mfma launch");
 }
 
 template <typename T>
 int launch(const C1mArgs& a, bool pool, hipStream_t st) {
-  return pool ? launch_t<T, true>(a, st) : launch_t<T, false>(a, st);
+  const bool par = a.pad_l & 1;
+  if (pool) return par ? launch_t<T, true, 1>(a, st) : launch_t<T, true, 0>(a, st);
+  return par ? launch_t<T, false, 1>(a, st) : launch_t<T, false, 0>(a, st);
 }
 
 }  // namespace

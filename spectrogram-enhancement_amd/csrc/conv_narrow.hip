@@ -24,14 +24,13 @@
 #include <cstdint>
 #include <string>
 
+#include "mma.hpp"
 #include "specenh.h"
 #include "runtime.hpp"
 
 namespace specenh {
 
 namespace {
-
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 struct NarrowArgs {
   const void* in;
@@ -47,32 +46,9 @@ struct NarrowArgs {
   int band_steps;  // conv_co1_kernel: TR-row steps per workgroup (blockIdx.y = band)
 };
 
-__device__ __forceinline__ float act_f(float v, int act) {
-  if (act == SPECENH_ACT_RELU) return fmaxf(v, 0.f);
-  if (act == SPECENH_ACT_SIGMOID) return 1.f / (1.f + __expf(-v));
-  return v;
-}
-
-template <typename T>
-__device__ __forceinline__ uint32_t tbits(T x) {
-  return (uint32_t)__builtin_bit_cast(unsigned short, x);
-}
 template <typename T>
 __device__ __forceinline__ T from_bits(uint32_t b) {
   return __builtin_bit_cast(T, (unsigned short)b);
-}
-
-// c + a.lo*b.lo + a.hi*b.hi for two packed 16-bit values of T
-template <typename T>
-__device__ __forceinline__ float dot2(uint32_t a, uint32_t b, float c) {
-  if constexpr (__is_same(T, _Float16)) {
-    return __builtin_amdgcn_fdot2(__builtin_bit_cast(f16x2, a), __builtin_bit_cast(f16x2, b), c,
-                                  false);
-  } else {  // v_dot2c_f32_bf16 (gfx950)
-    typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-    return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(b2, a), __builtin_bit_cast(b2, b), c,
-                                          false);
-  }
 }
 
 // ------------------------------------------------------------------ C == 1
@@ -125,8 +101,8 @@ __global__ __launch_bounds__(256) void conv_c1_kernel(NarrowArgs a) {
     uint32_t v = 0;
     if (co < a.CO && q < NQ) {
       const T* wr = W + (long long)co * K * K + ky * K;
-      v = tbits(wr[2 * j]);
-      if (2 * j + 1 < K) v |= tbits(wr[2 * j + 1]) << 16;
+      v = bits(wr[2 * j]);
+      if (2 * j + 1 < K) v |= bits(wr[2 * j + 1]) << 16;
     }
     sW[cl][q] = v;
   }
@@ -205,7 +181,7 @@ __global__ __launch_bounds__(256) void conv_c1_kernel(NarrowArgs a) {
       if (v01 > b) { b = v01; q = 1; }
       if (v10 > b) { b = v10; q = 2; }
       if (v11 > b) { b = v11; q = 3; }
-      pk[0][0][cl >> 1] |= tbits((T)b) << (16 * (cl & 1));
+      pk[0][0][cl >> 1] |= bits((T)b) << (16 * (cl & 1));
       am[cl >> 2] |= q << (8 * (cl & 3));
     } else {
 #pragma unroll
@@ -216,7 +192,7 @@ __global__ __launch_bounds__(256) void conv_c1_kernel(NarrowArgs a) {
           if (a.out_f32) {
             if (okpix[dy][dx] && cl < nco) reinterpret_cast<float*>(a.out)[opix[dy][dx] + cl] = v;
           } else {
-            pk[dy][dx][cl >> 1] |= tbits((T)v) << (16 * (cl & 1));
+            pk[dy][dx][cl >> 1] |= bits((T)v) << (16 * (cl & 1));
           }
         }
     }
@@ -261,7 +237,7 @@ __global__ __launch_bounds__(256) void conv_c1_kernel(NarrowArgs a) {
           } else {
 #pragma unroll
             for (int i = 0; i < 8; ++i) m8[i] = 0u;
-            for (int cl = 0; cl < nco; ++cl) m8[cl >> 1] |= tbits(mk[cl]) << (16 * (cl & 1));
+            for (int cl = 0; cl < nco; ++cl) m8[cl >> 1] |= bits(mk[cl]) << (16 * (cl & 1));
           }
 #pragma unroll
           for (int i = 0; i < 8; ++i) {
@@ -483,19 +459,6 @@ int launch_co1(const NarrowArgs& a, hipStream_t st) {
 #ifndef SPECENH_CO1M_R
 #define SPECENH_CO1M_R 8
 #endif
-typedef _Float16 f16x8m __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8m __attribute__((ext_vector_type(8)));
-typedef float f32x4m __attribute__((ext_vector_type(4)));
-template <typename T>
-__device__ __forceinline__ f32x4m mfma16(const uint4& a, const uint4& b, f32x4m acc) {
-  if constexpr (__is_same(T, _Float16))
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8m, a),
-                                                  __builtin_bit_cast(f16x8m, b), acc, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8m, a),
-                                                   __builtin_bit_cast(bf16x8m, b), acc, 0, 0, 0);
-}
-
 template <typename T, int NKS, int K>
 __global__ __launch_bounds__(256) void conv_co1m_kernel(NarrowArgs a) {
   constexpr int C = 32 * NKS, R = SPECENH_CO1M_R, P = K / 2, NIR = R + K - 1;
@@ -522,9 +485,9 @@ __global__ __launch_bounds__(256) void conv_co1m_kernel(NarrowArgs a) {
         wf[ky][ks] = m < K ? *reinterpret_cast<const uint4*>(W + ((ky * K + m) * C) + 32 * ks + 8 * kg)
                            : uint4{0u, 0u, 0u, 0u};
   }
-  f32x4m acc[R][2];
+  f32x4 acc[R][2];
 #pragma unroll
-  for (int o = 0; o < R; ++o) acc[o][0] = acc[o][1] = f32x4m{0.f, 0.f, 0.f, 0.f};
+  for (int o = 0; o < R; ++o) acc[o][0] = acc[o][1] = f32x4{0.f, 0.f, 0.f, 0.f};
   // B fragments of input row iy: tile t, position x' = x0 - 8 + 16 t + m, channels of k-step
   auto load_row = [&](int iy, uint4 (&b)[2][NKS]) {
 #pragma unroll
@@ -551,7 +514,7 @@ __global__ __launch_bounds__(256) void conv_co1m_kernel(NarrowArgs a) {
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) acc[o][t] = mfma16<T>(wf[ky][ks], bc[t][ks], acc[o][t]);
+        for (int ks = 0; ks < NKS; ++ks) acc[o][t] = mfma16x16x32<T>(wf[ky][ks], bc[t][ks], acc[o][t]);
     }
     if (ir + 1 < NIR) {
 #pragma unroll

@@ -36,6 +36,7 @@
 #include <type_traits>
 
 #include "lds_dma.hpp"
+#include "mma.hpp"
 #include "specenh.h"
 #include "runtime.hpp"
 #include "wave.hpp"
@@ -43,30 +44,6 @@
 namespace specenh {
 
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-template <typename T>
-__device__ __forceinline__ f32x4 mfma(const uint4& a, const uint4& b, f32x4 acc) {
-  if constexpr (__is_same(T, _Float16))
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a),
-                                                  __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a),
-                                                   __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
-}
-
-// two fp32 -> one packed pair of T (round to nearest even) as ONE v_cvt_pk_{f16,bf16}_f32;
-// the element-wise form became two converts plus a shift and an or
-template <typename T>
-__device__ __forceinline__ uint32_t pack2(float lo, float hi) {
-  typedef float f2 __attribute__((ext_vector_type(2)));
-  typedef T t2 __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f2{lo, hi}, t2));
-}
-
 
 // max with the neighbouring lane (m ^ 1): DPP quad_perm [1, 0, 3, 2]
 __device__ __forceinline__ float max_pair(float v) {
@@ -372,7 +349,7 @@ void conv_rows_pool_kernel(CRArgs a) {
         for (int i = 0; i < 4; ++i) v[i] = fmaxf(max_pair(fmaxf(r0[i], r1[i])), 0.f);
         r0 = bias;
         r1 = bias;
-        return uint2{pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3])};
+        return uint2{pack2_cvt<T>(v[0], v[1]), pack2_cvt<T>(v[2], v[3])};
       };
       // lanes m, m ^ 1 hold the same pooled values: both store them (no exec-mask branch)
       auto store = [&](const uint2 pk) {
@@ -383,7 +360,7 @@ void conv_rows_pool_kernel(CRArgs a) {
       };
       auto mm = [&](int j, int kx, int ky) {
         f32x4& ac = acc[slot(j + K / 2 - ky)];
-        ac = mfma<T>(wf[ky * K + kx], bf[P][j][kx], ac);
+        ac = mfma16x16x32<T>(wf[ky * K + kx], bf[P][j][kx], ac);
       };
       if (fl & 1u) {
         // first the row-0 MFMAs into the accumulators that are still summing (d <= 1); the
@@ -477,7 +454,7 @@ void conv_rows_pool_kernel(CRArgs a) {
           // lanes m, m ^ 1 hold the same pooled values: both store them (no exec-mask branch)
           const long long n = (long long)blockIdx.x + (long long)il * G;
           const long long o = ((n * PHh + q) * PW + (x0 + m) / 2) * COUT + 16 * nb + 4 * kg;
-          *reinterpret_cast<uint2*>(O + o) = uint2{pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3])};
+          *reinterpret_cast<uint2*>(O + o) = uint2{pack2_cvt<T>(v[0], v[1]), pack2_cvt<T>(v[2], v[3])};
         }
       }
       r0 = bias;
@@ -526,24 +503,24 @@ void conv_rows_pool_kernel(CRArgs a) {
 #pragma unroll
             for (int ky = 0; ky < K; ++ky) {
               f32x4& ac = acc[slot(j + K / 2 - ky)];
-              ac = mfma<T>(wf[ky * K + kx], bf[j][kx], ac);
+              ac = mfma16x16x32<T>(wf[ky * K + kx], bf[j][kx], ac);
             }
         } else {
           // consecutive MFMAs into different accumulators (no back-to-back dependency)
 #pragma unroll
           for (int ky = 0; ky < 5; ++ky) {
             f32x4& ac = acc[slot(j + 2 - ky)];
-            ac = mfma<T>(wf[ky], bf[j][0], ac);
+            ac = mfma16x16x32<T>(wf[ky], bf[j][0], ac);
           }
 #pragma unroll
           for (int ky = 0; ky < 5; ++ky) {
             f32x4& ac = acc[slot(j + 2 - ky)];
-            ac = mfma<T>(wf[5 + ky], bf[j][1], ac);
+            ac = mfma16x16x32<T>(wf[5 + ky], bf[j][1], ac);
           }
-          acc[slot(j + 2)] = mfma<T>(wf[10], bf[j][2], acc[slot(j + 2)]);
-          acc[slot(j)] = mfma<T>(wf[11], bf[j][2], acc[slot(j)]);
-          acc[slot(j - 2)] = mfma<T>(wf[12], bf[j][2], acc[slot(j - 2)]);
-          if (j == 0 && q == 0) acc[slot(1)] = mfma<T>(wf[10], bT, acc[slot(1)]);
+          acc[slot(j + 2)] = mfma16x16x32<T>(wf[10], bf[j][2], acc[slot(j + 2)]);
+          acc[slot(j)] = mfma16x16x32<T>(wf[11], bf[j][2], acc[slot(j)]);
+          acc[slot(j - 2)] = mfma16x16x32<T>(wf[12], bf[j][2], acc[slot(j - 2)]);
+          if (j == 0 && q == 0) acc[slot(1)] = mfma16x16x32<T>(wf[10], bT, acc[slot(1)]);
         }
       }
     }
@@ -577,18 +554,11 @@ template <typename T, int CIN, int COUT, int W, int K = 5, int SCHED = 0>
 hipError_t launch_rows(const CRArgs& a, hipStream_t st) {
   using C = RC<CIN, COUT, W, K>;
   const void* k = reinterpret_cast<const void*>(&conv_rows_pool_kernel<T, CIN, COUT, W, K, SCHED>);
-  static int per_cu[64] = {};
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
+  static ResidentSlots site;
+  long long slots = 0;
+  const hipError_t e = resident_slots(site, k, C::THREADS, C::LDS, &slots);
   if (e != hipSuccess) return e;
-  if (dev < 0 || dev >= 64) dev = 0;
-  if (per_cu[dev] == 0) {
-    int pc = 0;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, k, C::THREADS, C::LDS);
-    if (e != hipSuccess) return e;
-    per_cu[dev] = std::max(1, pc);
-  }
-  const long long grid = std::min<long long>(a.N, (long long)per_cu[dev] * device_cus());
+  const long long grid = std::min<long long>(a.N, slots);
   SPECENH_LAUNCH((conv_rows_pool_kernel<T, CIN, COUT, W, K, SCHED>), dim3((unsigned)grid),
                  dim3(C::THREADS), C::LDS, st, a);
   return hipGetLastError();
@@ -656,7 +626,7 @@ __device__ __forceinline__ uint32_t relu2(uint32_t p) {
 }
 template <typename T>
 __device__ __forceinline__ uint2 relu_pack4(const f32x4& v) {
-  return uint2{relu2<T>(pack2<T>(v[0], v[1])), relu2<T>(pack2<T>(v[2], v[3]))};
+  return uint2{relu2<T>(pack2_cvt<T>(v[0], v[1])), relu2<T>(pack2_cvt<T>(v[2], v[3]))};
 }
 
 // LEAD: ring refills in flight beyond the one a step waits for. Step g needs positions
@@ -786,11 +756,11 @@ void convt_rows_kernel(CRArgs a) {
           const uint4 b1 = *reinterpret_cast<const uint4*>(src + (xo[dx + 1] ^ 64));
 #pragma unroll
           for (int ph = 0; ph < 4; ++ph)
-            if (ttap(ph, dy, dx)) acc[ph] = mfma<T>(wf[u0[ph]], b0, acc[ph]);
+            if (ttap(ph, dy, dx)) acc[ph] = mfma16x16x32<T>(wf[u0[ph]], b0, acc[ph]);
 #pragma unroll
           for (int ph = 0; ph < 4; ++ph)
             if (ttap(ph, dy, dx)) {
-              acc[ph] = mfma<T>(wf[u0[ph] + 1], b1, acc[ph]);
+              acc[ph] = mfma16x16x32<T>(wf[u0[ph] + 1], b1, acc[ph]);
               u0[ph] += 2;
             }
         }
@@ -943,11 +913,11 @@ void convt_rows_pw_store8_kernel(CRArgs a) {
           const uint4 b1 = *reinterpret_cast<const uint4*>(src + (xo[dx + 1] ^ 64));
 #pragma unroll
           for (int ph = 0; ph < 4; ++ph)
-            if (ttap(ph, dy, dx)) acc[ph] = mfma<T>(wf[u0[ph]], b0, acc[ph]);
+            if (ttap(ph, dy, dx)) acc[ph] = mfma16x16x32<T>(wf[u0[ph]], b0, acc[ph]);
 #pragma unroll
           for (int ph = 0; ph < 4; ++ph)
             if (ttap(ph, dy, dx)) {
-              acc[ph] = mfma<T>(wf[u0[ph] + 1], b1, acc[ph]);
+              acc[ph] = mfma16x16x32<T>(wf[u0[ph] + 1], b1, acc[ph]);
               u0[ph] += 2;
             }
         }
@@ -1140,11 +1110,11 @@ void convt_rows_pw_kernel(CRArgs a) {
           const uint4 b1 = *reinterpret_cast<const uint4*>(src + (xo[dx + 1] ^ 64));
 #pragma unroll
           for (int ph = 0; ph < 4; ++ph)
-            if (ttap(ph, dy, dx)) acc[ph] = mfma<T>(wf[u0[ph]], b0, acc[ph]);
+            if (ttap(ph, dy, dx)) acc[ph] = mfma16x16x32<T>(wf[u0[ph]], b0, acc[ph]);
 #pragma unroll
           for (int ph = 0; ph < 4; ++ph)
             if (ttap(ph, dy, dx)) {
-              acc[ph] = mfma<T>(wf[u0[ph] + 1], b1, acc[ph]);
+              acc[ph] = mfma16x16x32<T>(wf[u0[ph] + 1], b1, acc[ph]);
               u0[ph] += 2;
             }
         }
@@ -1325,8 +1295,8 @@ void convt_rows_pg_kernel(CRArgs a) {
 #pragma unroll
             for (int q = 0; q < 2; ++q)
               if (ttap(PHS[q], dy, dx)) {
-                acc[q] = mfma<T>(wf[u0[q]], bq[3 * (dy + 1) + dx + 1][0], acc[q]);
-                acc[q] = mfma<T>(wf[u0[q] + 1], bq[3 * (dy + 1) + dx + 1][1], acc[q]);
+                acc[q] = mfma16x16x32<T>(wf[u0[q]], bq[3 * (dy + 1) + dx + 1][0], acc[q]);
+                acc[q] = mfma16x16x32<T>(wf[u0[q] + 1], bq[3 * (dy + 1) + dx + 1][1], acc[q]);
                 u0[q] += 2;
               }
 #pragma unroll
@@ -1384,21 +1354,11 @@ hipError_t launch_convt_rows_pw(const CRArgs& a0, hipStream_t st) {
   const void* k = STORE8 ? reinterpret_cast<const void*>(&convt_rows_pw_store8_kernel<T, 3>)
                          : reinterpret_cast<const void*>(&convt_rows_pw_kernel<T, 3>);
   static LdsOptIn lds_site;
-  static std::atomic<int> per_cu[64];  // resident workgroups per CU (0 = not queried)
+  static ResidentSlots site;
+  long long slots = 0;
   hipError_t e = allow_lds(lds_site, {k}, LDS);
+  if (e == hipSuccess) e = resident_slots(site, k, 256, LDS, &slots);
   if (e != hipSuccess) return e;
-  int dev = 0;
-  e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  if (dev < 0 || dev >= 64) dev = 0;
-  int pc = per_cu[dev].load(std::memory_order_relaxed);
-  if (pc == 0) {
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, k, 256, LDS);
-    if (e != hipSuccess) return e;
-    pc = std::max(1, pc);
-    per_cu[dev].store(pc, std::memory_order_relaxed);  // same value from any racing thread
-  }
-  const long long slots = (long long)pc * device_cus();
   CRArgs a = a0;
   a.lgb = convt_row_bands_lg(a.N, a.H, slots);
   const long long grid = std::min<long long>((long long)a.N << a.lgb, slots);
@@ -1413,18 +1373,10 @@ template <typename T, int CO, int W, int LEAD>
 hipError_t launch_convt_rows_lead(const CRArgs& a0, hipStream_t st) {
   using C = TC<CO, W>;
   const void* k = reinterpret_cast<const void*>(&convt_rows_kernel<T, CO, W, LEAD>);
-  static int per_cu[64] = {};
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
+  static ResidentSlots site;
+  long long slots = 0;
+  const hipError_t e = resident_slots(site, k, C::THREADS, C::LDS, &slots);
   if (e != hipSuccess) return e;
-  if (dev < 0 || dev >= 64) dev = 0;
-  if (per_cu[dev] == 0) {
-    int pc = 0;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, k, C::THREADS, C::LDS);
-    if (e != hipSuccess) return e;
-    per_cu[dev] = std::max(1, pc);
-  }
-  const long long slots = (long long)per_cu[dev] * device_cus();
   CRArgs a = a0;
   a.lgb = convt_row_bands_lg(a.N, a.H, slots);
   const long long grid = std::min<long long>((long long)a.N << a.lgb, slots);
@@ -1596,7 +1548,7 @@ void convt_rows32_kernel(CRArgs a) {
           const uint4 b = *reinterpret_cast<const uint4*>(src + xo[dx - DY0]);
 #pragma unroll
           for (int ph = 0; ph < 4; ++ph)
-            if (C::tap(ph, dy, dx)) acc[ph] = mfma<T>(wf[C::tap_index(ph, dy, dx)], b, acc[ph]);
+            if (C::tap(ph, dy, dx)) acc[ph] = mfma16x16x32<T>(wf[C::tap_index(ph, dy, dx)], b, acc[ph]);
         }
       }
 #pragma unroll
@@ -1620,18 +1572,11 @@ hipError_t launch_convt_rows32(const CRArgs& a, hipStream_t st) {
   using C = TC32<CO, W, K>;
   constexpr int LEAD = 8 - C::NDY - 1 < 3 ? 8 - C::NDY - 1 : 3;
   const void* k = reinterpret_cast<const void*>(&convt_rows32_kernel<T, CO, W, K, LEAD>);
-  static int per_cu[64] = {};
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
+  static ResidentSlots site;
+  long long slots = 0;
+  const hipError_t e = resident_slots(site, k, C::THREADS, C::LDS, &slots);
   if (e != hipSuccess) return e;
-  if (dev < 0 || dev >= 64) dev = 0;
-  if (per_cu[dev] == 0) {
-    int pc = 0;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, k, C::THREADS, C::LDS);
-    if (e != hipSuccess) return e;
-    per_cu[dev] = std::max(1, pc);
-  }
-  const long long grid = std::min<long long>(a.N, (long long)per_cu[dev] * device_cus());
+  const long long grid = std::min<long long>(a.N, slots);
   SPECENH_LAUNCH((convt_rows32_kernel<T, CO, W, K, LEAD>), dim3((unsigned)grid),
                  dim3(C::THREADS), C::LDS, st, a);
   return hipGetLastError();
@@ -1690,7 +1635,7 @@ __device__ __forceinline__ uint4 c1_afrag(const T* __restrict__ Wg, int m, int g
       const int ky = j < 6 ? g : 4, c = (j < 6 ? j : 2 * g + j - 6) - cb;
       v[h] = (j < 6 || g < 3) && c >= 0 && c <= 4 ? (float)Wg[(m * 5 + ky) * 5 + c] : 0.f;
     }
-    q[i] = pack2<T>(v[0], v[1]);
+    q[i] = pack2_cvt<T>(v[0], v[1]);
   }
   return uint4{q[0], q[1], q[2], q[3]};
 }
@@ -1770,10 +1715,10 @@ __global__ __launch_bounds__(256) void conv1_rows_pool_kernel(CRArgs a) {
       // output rows y = 2p + dy: both fragments before the first MFMA
       const uint4 b0 = bfrag(pb), b1 = bfrag(pb + 1);
       f32x4 acc[2][2];
-      acc[0][0] = mfma<T>(w0, b0, bias);
-      acc[0][1] = mfma<T>(w1, b0, bias);
-      acc[1][0] = mfma<T>(w0, b1, bias);
-      acc[1][1] = mfma<T>(w1, b1, bias);
+      acc[0][0] = mfma16x16x32<T>(w0, b0, bias);
+      acc[0][1] = mfma16x16x32<T>(w1, b0, bias);
+      acc[1][0] = mfma16x16x32<T>(w0, b1, bias);
+      acc[1][1] = mfma16x16x32<T>(w1, b1, bias);
       float v[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i)
@@ -1781,7 +1726,7 @@ __global__ __launch_bounds__(256) void conv1_rows_pool_kernel(CRArgs a) {
                      0.f);
       const long long n = (long long)blockIdx.x + (long long)il * G;
       *reinterpret_cast<uint2*>(O + ((n * PH + p) * PW + 16 * wv + m) * 16 + 4 * kg) =
-          uint2{pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3])};
+          uint2{pack2_cvt<T>(v[0], v[1]), pack2_cvt<T>(v[2], v[3])};
     }
     // wave 0: the DMAs of step g - 1 (positions 2g + 8, 2g + 9, first read at step g + 2) must
     // land before the barrier; this step's DMAs and its store are the youngest vector-memory
@@ -1800,18 +1745,11 @@ __global__ __launch_bounds__(256) void conv1_rows_pool_kernel(CRArgs a) {
 template <typename T>
 hipError_t launch_conv1_rows(const CRArgs& a, hipStream_t st) {
   const void* k = reinterpret_cast<const void*>(&conv1_rows_pool_kernel<T>);
-  static int per_cu[64] = {};
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
+  static ResidentSlots site;
+  long long slots = 0;
+  const hipError_t e = resident_slots(site, k, 256, C1LDS, &slots);
   if (e != hipSuccess) return e;
-  if (dev < 0 || dev >= 64) dev = 0;
-  if (per_cu[dev] == 0) {
-    int pc = 0;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, k, 256, C1LDS);
-    if (e != hipSuccess) return e;
-    per_cu[dev] = std::max(1, pc);
-  }
-  const long long grid = std::min<long long>(a.N, (long long)per_cu[dev] * device_cus());
+  const long long grid = std::min<long long>(a.N, slots);
   SPECENH_LAUNCH(conv1_rows_pool_kernel<T>, dim3((unsigned)grid), dim3(256), C1LDS, st, a);
   return hipGetLastError();
 }
@@ -2003,7 +1941,7 @@ void enc2_rows_kernel(E2Args a) {
   auto c1_window = [&](float (&v)[4], const uint4& bA, const uint4& bB, const f32x4& bias1) {
 #pragma unroll
     for (int pr = 0; pr < 4; ++pr) {
-      const f32x4 acc1 = mfma<T>(pr & 1 ? v1 : v0, pr >> 1 ? bB : bA, bias1);
+      const f32x4 acc1 = mfma16x16x32<T>(pr & 1 ? v1 : v0, pr >> 1 ? bB : bA, bias1);
 #pragma unroll
       for (int i = 0; i < 4; ++i) v[i] = fmaxf(v[i], acc1[i]);
     }
@@ -2020,7 +1958,7 @@ void enc2_rows_kernel(E2Args a) {
     const uint4 bA = bfrag(pb), bB = bfrag(pb + 1);
     c1_window(v, bA, bB, *reinterpret_cast<const f32x4*>(btab + 4 * kg));
     const bool real = il < nimg && r < H;
-    const uint2 pk = real ? uint2{pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3])} : uint2{0u, 0u};
+    const uint2 pk = real ? uint2{pack2_cvt<T>(v[0], v[1]), pack2_cvt<T>(v[2], v[3])} : uint2{0u, 0u};
     *reinterpret_cast<uint2*>(ring + ((2 * g2 + jr) & 7) * C::ROWB + (16 * w1x + m + 2) * 32 +
                               8 * kg) = pk;
   };
@@ -2175,7 +2113,7 @@ void enc2_rows_kernel(E2Args a) {
       float v[4] = {0.f, 0.f, 0.f, 0.f};
       auto c2 = [&](int j, int w, const uint4& b) {  // weight fragment w of row j: its output row
         const int d = w < 10 ? j + 2 - w % 5 : w == 10 ? j + 2 : w == 11 ? j : j - 2;
-        acc[slot(d)] = mfma<T>(wf[w], b, acc[slot(d)]);
+        acc[slot(d)] = mfma16x16x32<T>(wf[w], b, acc[slot(d)]);
       };
       {  // pair s - 2: pool on the packed pairs (rows in lane, columns across the lane pair
          // m, m ^ 1, ReLU), reset, into the tile: unconditionally, a tile no flag marks is
@@ -2183,8 +2121,8 @@ void enc2_rows_kernel(E2Args a) {
         auto nbr = [](uint32_t x) {
           return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0xB1, 0xF, 0xF, true);
         };
-        const uint32_t p0 = max_s16x2(pack2<T>(r0[0], r0[1]), pack2<T>(r1[0], r1[1]));
-        const uint32_t p1 = max_s16x2(pack2<T>(r0[2], r0[3]), pack2<T>(r1[2], r1[3]));
+        const uint32_t p0 = max_s16x2(pack2_cvt<T>(r0[0], r0[1]), pack2_cvt<T>(r1[0], r1[1]));
+        const uint32_t p1 = max_s16x2(pack2_cvt<T>(r0[2], r0[3]), pack2_cvt<T>(r1[2], r1[3]));
         const f32x4 bias = bias2_ld();
         r0 = bias;
         r1 = bias;
@@ -2204,11 +2142,11 @@ void enc2_rows_kernel(E2Args a) {
 #pragma unroll
         for (int w = 5; w < 10; ++w) c2(j, w, b2);
         c2(j, 10, bF); c2(j, 11, bF); c2(j, 12, bF);
-        if (j == 0) acc[slot(1)] = mfma<T>(wf[10], ld16(ring + foT), acc[slot(1)]);
+        if (j == 0) acc[slot(1)] = mfma16x16x32<T>(wf[10], ld16(ring + foT), acc[slot(1)]);
       }
       // conv2 input row 2 q + jr of step s + 2 into its ring slot (zeros outside the image)
       {
-        const uint2 pv = uint2{pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3])};
+        const uint2 pv = uint2{pack2_cvt<T>(v[0], v[1]), pack2_cvt<T>(v[2], v[3])};
         const uint32_t keep = 0u - (flc & F_PROD);
         *reinterpret_cast<uint2*>(ring + ((2 * s + 4 + jr) & 7) * C::ROWB + (16 * w1x + m + 2) * 32 +
                                   8 * kg) = uint2{pv.x & keep, pv.y & keep};
@@ -2264,7 +2202,7 @@ void enc2_rows_kernel(E2Args a) {
           // pixel: no exec-mask branch around the store
           const long long n = (long long)blockIdx.x + (long long)il * G;
           const long long o = ((n * PHh + q) * PW + (x0 + m) / 2) * 32 + 16 * nb + 4 * kg;
-          *reinterpret_cast<uint2*>(O + o) = uint2{pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3])};
+          *reinterpret_cast<uint2*>(O + o) = uint2{pack2_cvt<T>(v[0], v[1]), pack2_cvt<T>(v[2], v[3])};
         }
       }
       const f32x4 bias = bias2_ld();
@@ -2295,20 +2233,20 @@ void enc2_rows_kernel(E2Args a) {
 #pragma unroll
       for (int ky = 0; ky < 5; ++ky) {
         f32x4& ac = acc[slot(j + 2 - ky)];
-        ac = mfma<T>(wf[ky], b0, ac);
+        ac = mfma16x16x32<T>(wf[ky], b0, ac);
       }
 #pragma unroll
       for (int ky = 0; ky < 5; ++ky) {
         f32x4& ac = acc[slot(j + 2 - ky)];
-        ac = mfma<T>(wf[5 + ky], b2, ac);
+        ac = mfma16x16x32<T>(wf[5 + ky], b2, ac);
       }
-      acc[slot(j + 2)] = mfma<T>(wf[10], bF, acc[slot(j + 2)]);
-      acc[slot(j)] = mfma<T>(wf[11], bF, acc[slot(j)]);
-      acc[slot(j - 2)] = mfma<T>(wf[12], bF, acc[slot(j - 2)]);
+      acc[slot(j + 2)] = mfma16x16x32<T>(wf[10], bF, acc[slot(j + 2)]);
+      acc[slot(j)] = mfma16x16x32<T>(wf[11], bF, acc[slot(j)]);
+      acc[slot(j - 2)] = mfma16x16x32<T>(wf[12], bF, acc[slot(j - 2)]);
       if (j == 0) {  // F(-1) at the top of an image (q == 0), zero otherwise
         uint4 bT = *reinterpret_cast<const uint4*>(ring + ((2 * s) & 7) * C::ROWB + fo);
         if (kg < 2 || q != 0) bT = uint4{0u, 0u, 0u, 0u};
-        acc[slot(1)] = mfma<T>(wf[10], bT, acc[slot(1)]);
+        acc[slot(1)] = mfma16x16x32<T>(wf[10], bT, acc[slot(1)]);
       }
     }
     };
@@ -2373,18 +2311,11 @@ template <typename T, int WPE, int SCHED>
 hipError_t launch_enc2_wpe(const E2Args& a, hipStream_t st) {
   constexpr int LDSB = SCHED == 1 ? E2LDS1 : E2LDS;
   const void* k = reinterpret_cast<const void*>(&enc2_rows_kernel<T, WPE, SCHED>);
-  static int per_cu[64] = {};
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
+  static ResidentSlots site;
+  long long slots = 0;
+  const hipError_t e = resident_slots(site, k, 512, LDSB, &slots);
   if (e != hipSuccess) return e;
-  if (dev < 0 || dev >= 64) dev = 0;
-  if (per_cu[dev] == 0) {
-    int pc = 0;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, k, 512, LDSB);
-    if (e != hipSuccess) return e;
-    per_cu[dev] = std::max(1, pc);
-  }
-  const long long grid = std::min<long long>(a.N, (long long)per_cu[dev] * device_cus());
+  const long long grid = std::min<long long>(a.N, slots);
   SPECENH_LAUNCH((enc2_rows_kernel<T, WPE, SCHED>), dim3((unsigned)grid), dim3(512), LDSB, st, a);
   return hipGetLastError();
 }
@@ -2399,6 +2330,13 @@ hipError_t launch_enc2(const E2Args& a, hipStream_t st) {
   return launch_enc2_wpe<T, 4, 0>(a, st);
 }
 
+// an entry's result from its launch's: *launched on success, the HIP error under `what` otherwise
+int rows_result(hipError_t e, const char* what, bool* launched) {
+  if (e != hipSuccess) return set_error(SPECENH_EHIP, std::string(what) + ": " + hipGetErrorString(e));
+  *launched = true;
+  return SPECENH_OK;
+}
+
 }  // namespace
 
 // The row-sweep kernel for an inference Conv2D(5, relu, same) + MaxPooling2D(2) when the
@@ -2409,31 +2347,22 @@ int conv_rows_pool(int dtype, const void* x, int N, int H, int W, int CI, const 
   *launched = false;
   if (variant(V_CONV_NO_ROWS) != 0 || N <= 0 || H < 2 || (H & 1) || !b) return SPECENH_OK;
   if ((long long)N * H * W * CI >= (1ll << 31)) return SPECENH_OK;
-  CRArgs a{};
-  a.x = x; a.w = w; a.b = b; a.out = out; a.N = N; a.H = H;
-  hipError_t e = hipSuccess;
-  const bool f16 = dtype == SPECENH_DTYPE_F16;
   if (dtype != SPECENH_DTYPE_F16 && dtype != SPECENH_DTYPE_BF16) return SPECENH_OK;
-  if (CI == 16 && CO == 32 && W == 64 && K == 5)
-    e = f16 ? launch_rows<_Float16, 16, 32, 64>(a, st) : launch_rows<__bf16, 16, 32, 64>(a, st);
-  else if (CI == 32 && CO == 64 && W == 32 && K == 5 && variant(V_CONV_ROWS_SCHED) != 0)
-    e = f16 ? launch_rows<_Float16, 32, 64, 32, 5, 1>(a, st) : launch_rows<__bf16, 32, 64, 32, 5, 1>(a, st);
-  else if (CI == 32 && CO == 64 && W == 32 && K == 5)
-    e = f16 ? launch_rows<_Float16, 32, 64, 32>(a, st) : launch_rows<__bf16, 32, 64, 32>(a, st);
-  else if (CI == 32 && CO == 32 && W == 64 && K == 5)  // hyperparam_scan.py, 256 x 128 inputs
-    e = f16 ? launch_rows<_Float16, 32, 32, 64>(a, st) : launch_rows<__bf16, 32, 32, 64>(a, st);
-  else if (CI == 32 && CO == 32 && W == 64 && K == 3)
-    e = f16 ? launch_rows<_Float16, 32, 32, 64, 3>(a, st) : launch_rows<__bf16, 32, 32, 64, 3>(a, st);
-  else
-    return SPECENH_OK;
-  if (e != hipSuccess) return set_error(SPECENH_EHIP, std::string("conv_rows: ") + hipGetErrorString(e));
-  *launched = true;
-  return SPECENH_OK;
+  const CRArgs a{x, w, b, out, N, H, 0};
+  const bool k5 = K == 5, covered = (CI == 16 && CO == 32 && W == 64 && k5) ||
+                                    (CI == 32 && CO == 64 && W == 32 && k5) ||
+                                    (CI == 32 && CO == 32 && W == 64 && (k5 || K == 3));
+  if (!covered) return SPECENH_OK;
+  const hipError_t e = with_half_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (CI == 16) return launch_rows<T, 16, 32, 64>(a, st);
+    if (CO == 64) return variant(V_CONV_ROWS_SCHED) != 0 ? launch_rows<T, 32, 64, 32, 5, 1>(a, st)
+                                                         : launch_rows<T, 32, 64, 32>(a, st);
+    // hyperparam_scan.py, 256 x 128 inputs
+    return k5 ? launch_rows<T, 32, 32, 64>(a, st) : launch_rows<T, 32, 32, 64, 3>(a, st);
+  });
+  return rows_result(e, "conv_rows", launched);
 }
-
-}  // namespace specenh
-
-namespace specenh {
 
 // The row-sweep kernel for Conv2DTranspose(CO, 5, s2, relu, same) on 64-channel inputs of
 // width 16 (CO 64) or 32 (CO 32), forward (any batch); *launched = false otherwise.
@@ -2443,43 +2372,28 @@ int convt_rows(int dtype, const void* x, int N, int H, int W, int CI, const void
   if (variant(V_CONVT_NO_ROWS) != 0 || N <= 0 || H <= 0 || !b) return SPECENH_OK;
   if (dtype != SPECENH_DTYPE_F16 && dtype != SPECENH_DTYPE_BF16) return SPECENH_OK;
   if ((long long)N * 4 * H * W * CO >= (1ll << 31)) return SPECENH_OK;
-  CRArgs a{};
-  a.x = x; a.w = w; a.b = b; a.out = out; a.N = N; a.H = H;
-  const bool f16 = dtype == SPECENH_DTYPE_F16;
-  hipError_t e;
+  const CRArgs a{x, w, b, out, N, H, 0};
   if (CI == 32) {  // the scan models' first Conv2DTranspose (32 -> 32 on 32-position rows)
-    if (CO != 32 || W != 32) return SPECENH_OK;
-    if (K == 3) e = f16 ? launch_convt_rows32<_Float16, 32, 32, 3>(a, st) : launch_convt_rows32<__bf16, 32, 32, 3>(a, st);
-    else if (K == 5) e = f16 ? launch_convt_rows32<_Float16, 32, 32, 5>(a, st) : launch_convt_rows32<__bf16, 32, 32, 5>(a, st);
-    else if (K == 7) e = f16 ? launch_convt_rows32<_Float16, 32, 32, 7>(a, st) : launch_convt_rows32<__bf16, 32, 32, 7>(a, st);
-    else return SPECENH_OK;
-    if (e != hipSuccess) return set_error(SPECENH_EHIP, std::string("convt_rows32: ") + hipGetErrorString(e));
-    *launched = true;
-    return SPECENH_OK;
+    if (CO != 32 || W != 32 || (K != 3 && K != 5 && K != 7)) return SPECENH_OK;
+    const hipError_t e = with_half_type(dtype, [&](auto t) {
+      using T = decltype(t);
+      return K == 3   ? launch_convt_rows32<T, 32, 32, 3>(a, st)
+             : K == 5 ? launch_convt_rows32<T, 32, 32, 5>(a, st)
+                      : launch_convt_rows32<T, 32, 32, 7>(a, st);
+    });
+    return rows_result(e, "convt_rows32", launched);
   }
-  if (CI != 64 || K != 5) return SPECENH_OK;
-  if (CO == 64 && W == 16 && variant(V_CONVT_SHARED_RING) == 0 && variant(V_CONVT_PG) != 0)
-    e = f16 ? launch_convt_rows_pg<_Float16>(a, st) : launch_convt_rows_pg<__bf16>(a, st);
-  else if (CO == 64 && W == 16 && variant(V_CONVT_SHARED_RING) == 0 && variant(V_CONVT_STORE8) != 0)
-    e = f16 ? launch_convt_rows_pw<_Float16, true>(a, st)
-            : launch_convt_rows_pw<__bf16, true>(a, st);
-  else if (CO == 64 && W == 16 && variant(V_CONVT_SHARED_RING) == 0)
-    e = f16 ? launch_convt_rows_pw<_Float16, false>(a, st)
-            : launch_convt_rows_pw<__bf16, false>(a, st);
-  else if (CO == 64 && W == 16)
-    e = f16 ? launch_convt_rows<_Float16, 64, 16>(a, st) : launch_convt_rows<__bf16, 64, 16>(a, st);
-  else if (CO == 32 && W == 32)
-    e = f16 ? launch_convt_rows<_Float16, 32, 32>(a, st) : launch_convt_rows<__bf16, 32, 32>(a, st);
-  else
-    return SPECENH_OK;
-  if (e != hipSuccess) return set_error(SPECENH_EHIP, std::string("convt_rows: ") + hipGetErrorString(e));
-  *launched = true;
-  return SPECENH_OK;
+  if (CI != 64 || K != 5 || !((CO == 64 && W == 16) || (CO == 32 && W == 32))) return SPECENH_OK;
+  const hipError_t e = with_half_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (CO == 32) return launch_convt_rows<T, 32, 32>(a, st);
+    if (variant(V_CONVT_SHARED_RING) != 0) return launch_convt_rows<T, 64, 16>(a, st);
+    if (variant(V_CONVT_PG) != 0) return launch_convt_rows_pg<T>(a, st);
+    return variant(V_CONVT_STORE8) != 0 ? launch_convt_rows_pw<T, true>(a, st)
+                                        : launch_convt_rows_pw<T, false>(a, st);
+  });
+  return rows_result(e, "convt_rows", launched);
 }
-
-}  // namespace specenh
-
-namespace specenh {
 
 // The C = 1 row sweep for an inference Conv2D(16, 5, relu, same) + MaxPooling2D(2) on
 // 128-wide images; *launched = false otherwise (the caller runs conv_c1_mfma).
@@ -2490,13 +2404,10 @@ int conv1_rows_pool(int dtype, const void* x, int N, int H, int W, const void* w
     return SPECENH_OK;
   if (dtype != SPECENH_DTYPE_F16 && dtype != SPECENH_DTYPE_BF16) return SPECENH_OK;
   if (((uintptr_t)x & 15) || (long long)N * H * W >= (1ll << 31)) return SPECENH_OK;
-  CRArgs a{};
-  a.x = x; a.w = w; a.b = b; a.out = out; a.N = N; a.H = H;
-  const hipError_t e = dtype == SPECENH_DTYPE_F16 ? launch_conv1_rows<_Float16>(a, st)
-                                                  : launch_conv1_rows<__bf16>(a, st);
-  if (e != hipSuccess) return set_error(SPECENH_EHIP, std::string("conv1_rows: ") + hipGetErrorString(e));
-  *launched = true;
-  return SPECENH_OK;
+  const CRArgs a{x, w, b, out, N, H, 0};
+  const hipError_t e =
+      with_half_type(dtype, [&](auto t) { return launch_conv1_rows<decltype(t)>(a, st); });
+  return rows_result(e, "conv1_rows", launched);
 }
 
 }  // namespace specenh
@@ -2522,16 +2433,16 @@ extern "C" int specenh_encoder2(int dtype, const void* x, int N, int H, int W, c
   a.x = x; a.w1 = w1_gemm; a.b1 = b1; a.w2 = w2_gemm; a.b2 = b2; a.out = out; a.N = N; a.H = H;
   hipStream_t st = (hipStream_t)stream;
   static LdsOptIn lds_site;
-  (void)allow_lds(lds_site,
-                  {reinterpret_cast<const void*>(&enc2_rows_kernel<_Float16, 4, 1>),
-                   reinterpret_cast<const void*>(&enc2_rows_kernel<__bf16, 4, 1>),
-                   reinterpret_cast<const void*>(&enc2_rows_kernel<_Float16, 4, 0>),
-                   reinterpret_cast<const void*>(&enc2_rows_kernel<__bf16, 4, 0>),
-                   reinterpret_cast<const void*>(&enc2_rows_kernel<_Float16, 2, 0>),
-                   reinterpret_cast<const void*>(&enc2_rows_kernel<__bf16, 2, 0>)},
-                  E2LDS1);
-  const hipError_t e = dtype == SPECENH_DTYPE_F16 ? launch_enc2<_Float16>(a, st)
-                                                  : launch_enc2<__bf16>(a, st);
+  hipError_t e = allow_lds(lds_site,
+                           {reinterpret_cast<const void*>(&enc2_rows_kernel<_Float16, 4, 1>),
+                            reinterpret_cast<const void*>(&enc2_rows_kernel<__bf16, 4, 1>),
+                            reinterpret_cast<const void*>(&enc2_rows_kernel<_Float16, 4, 0>),
+                            reinterpret_cast<const void*>(&enc2_rows_kernel<__bf16, 4, 0>),
+                            reinterpret_cast<const void*>(&enc2_rows_kernel<_Float16, 2, 0>),
+                            reinterpret_cast<const void*>(&enc2_rows_kernel<__bf16, 2, 0>)},
+                           E2LDS1);
+  if (e == hipSuccess)
+    e = with_half_type(dtype, [&](auto t) { return launch_enc2<decltype(t)>(a, st); });
   if (e != hipSuccess) return set_error(SPECENH_EHIP, std::string("encoder2: ") + hipGetErrorString(e));
   return SPECENH_OK;
 }

@@ -38,6 +38,7 @@
 #include <vector>
 
 #include "lds_dma.hpp"
+#include "mma.hpp"
 #include "specenh.h"
 #include "runtime.hpp"
 #include "wave.hpp"
@@ -45,12 +46,6 @@
 namespace specenh {
 
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TO = 32;                 // final output pixels per tile side
 constexpr int NP = TO / 2 + 2;         // 18 input positions per side (one-position halo)
@@ -76,34 +71,6 @@ struct TailArgs {
 // tap row ky of neighbourhood offset dy for output row phase py (-1 <= dy <= 1; valid when
 // 0 <= ky < KT)
 __host__ __device__ constexpr int ky_of(int py, int dy) { return 2 * dy + PT - py; }
-
-template <typename T>
-__device__ __forceinline__ f32x4 mfma(const uint4& a, const uint4& b, f32x4 acc) {
-  if constexpr (__is_same(T, _Float16))
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a),
-                                                  __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a),
-                                                   __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
-}
-
-template <typename T>
-__device__ __forceinline__ float dot2(uint32_t a, uint32_t b, float c) {
-  if constexpr (__is_same(T, _Float16)) {
-    return __builtin_amdgcn_fdot2(__builtin_bit_cast(f16x2, a), __builtin_bit_cast(f16x2, b), c,
-                                  false);
-  } else {  // v_dot2c_f32_bf16 (gfx950)
-    return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, a),
-                                           __builtin_bit_cast(bf16x2, b), c, false);
-  }
-}
-
-template <typename T>
-__device__ __forceinline__ uint32_t pack2(float lo, float hi) {
-  const T a = (T)lo, b = (T)hi;
-  return (uint32_t)__builtin_bit_cast(unsigned short, a) |
-         ((uint32_t)__builtin_bit_cast(unsigned short, b) << 16);
-}
 
 // Phase PH = py * 2 + px: its taps in (dy, dx) order, compile-time (static register indices).
 template <int PH>
@@ -138,7 +105,7 @@ __device__ __forceinline__ f32x4 item_mfma(const uint4 (&wr)[9], const T* sp, f3
     for (int dx = -1; dx <= 1; ++dx)
       if (Taps<PH>::ok(dy, dx)) {
         const uint4 b = *reinterpret_cast<const uint4*>(sp + (dy * XW + dx) * XPST);
-        acc = mfma<T>(wr[u], b, acc);
+        acc = mfma16x16x32<T>(wr[u], b, acc);
         ++u;
       }
   return acc;
@@ -256,8 +223,8 @@ __device__ __forceinline__ void tail_body(const TailArgs& a, T* sx, T* sy, int w
       const int gy = g.oy0 - 2 + yy, gx = g.ox0 - 2 + yx;
       const bool in = (unsigned)gy < (unsigned)H2 && (unsigned)gx < (unsigned)W2;
       uint2 v;
-      v.x = in ? pack2<T>(fmaxf(acc[0] + bias[0], 0.f), fmaxf(acc[1] + bias[1], 0.f)) : 0u;
-      v.y = in ? pack2<T>(fmaxf(acc[2] + bias[2], 0.f), fmaxf(acc[3] + bias[3], 0.f)) : 0u;
+      v.x = in ? pack2_bits<T>(fmaxf(acc[0] + bias[0], 0.f), fmaxf(acc[1] + bias[1], 0.f)) : 0u;
+      v.y = in ? pack2_bits<T>(fmaxf(acc[2] + bias[2], 0.f), fmaxf(acc[3] + bias[3], 0.f)) : 0u;
       *reinterpret_cast<uint2*>(sy + ymap(yy * YW + yx, kg >> 1) + 4 * (kg & 1)) = v;
     }
     lds_barrier();  // the map is complete; every patch read is done
@@ -288,7 +255,7 @@ __device__ __forceinline__ void tail_body(const TailArgs& a, T* sx, T* sy, int w
             for (int s2 = 0; s2 < 3; ++s2) {
               const int row = min(yrow + 2 * s2 + (kg >> 1), YW - 1);  // row 5: zero weights
               const uint4 av = *reinterpret_cast<const uint4*>(sy + ymap(row * YW + xc, kg & 1));
-              acc = mfma<T>(av, wo_frag[s2], acc);
+              acc = mfma16x16x32<T>(av, wo_frag[s2], acc);
             }
             if (m < KO)  // D[x' = 16 xb + 4 kg + r][kx = m]
               *reinterpret_cast<f32x4*>(sp + (h * KO + m) * PXW + 16 * xb + 4 * kg) = acc;
@@ -393,23 +360,6 @@ struct RowsArgs {
   int N, H, R, nb;  // R: output rows per band (even), nb: bands per image
 };
 
-// bias + ReLU of four fp32 accumulators -> four T packed in 8 bytes. The accumulators start
-// at the bias (folded into the MFMA chain); ReLU commutes with the monotone rounding, so for
-// fp16 it runs on the packed halves (v_pk_max_f16: 2 instead of 4 VALU).
-template <typename T>
-__device__ __forceinline__ uint2 relu_pack(const f32x4& v) {
-  if constexpr (__is_same(T, _Float16)) {
-    const f16x2 lo = f16x2{(_Float16)v[0], (_Float16)v[1]};
-    const f16x2 hi = f16x2{(_Float16)v[2], (_Float16)v[3]};
-    const f16x2 z = f16x2{(_Float16)0.f, (_Float16)0.f};
-    return uint2{__builtin_bit_cast(uint32_t, __builtin_elementwise_max(lo, z)),
-                 __builtin_bit_cast(uint32_t, __builtin_elementwise_max(hi, z))};
-  } else {
-    return uint2{pack2<T>(fmaxf(v[0], 0.f), fmaxf(v[1], 0.f)),
-                 pack2<T>(fmaxf(v[2], 0.f), fmaxf(v[3], 0.f))};
-  }
-}
-
 // The last two layers' per-wave state and steps, shared by tail_rows_kernel and
 // decoder3_kernel: lane (m = lane & 15, kg = lane >> 4) of wave w (0..3) owns input
 // positions 16 w + m of a position row, i.e. map columns 32 w .. 32 w + 31. Ring slots are
@@ -484,7 +434,7 @@ struct TailWave {
         for (int ph = 0; ph < 4; ++ph) {
           const int ky = ky_of(ph >> 1, dy), kx = ky_of(ph & 1, dx);
           if (ky < 0 || ky >= KT || kx < 0 || kx >= KT) continue;
-          acc[ph] = mfma<T>(wt[u0[ph]++], b, acc[ph]);
+          acc[ph] = mfma16x16x32<T>(wt[u0[ph]++], b, acc[ph]);
         }
       }
 #pragma unroll
@@ -514,7 +464,7 @@ struct TailWave {
       for (int p = 0; p < 3; ++p) {
         // map row 2q - 4 + 2p + dr: lane groups kg >> 1 = 0 / 1 read the pair's two rows
         const uint4 av = *reinterpret_cast<const uint4*>(mrow(2 * p) + mrd[blk]);
-        d = mfma<T>(av, wo[p], d);
+        d = mfma16x16x32<T>(av, wo[p], d);
       }
       if (m < rows::SCR)  // D[x' = 32 w + 16 blk + 4 kg + i][n = m]
         *reinterpret_cast<f32x4*>(scb + scw[blk]) = d;
@@ -916,8 +866,8 @@ __global__ __launch_bounds__(512, 2) void decoder3_kernel(D3Args a) {
             for (int ph = 0; ph < 4; ++ph) {
               const int ky = ky_of(ph >> 1, dy), kx = ky_of(ph & 1, dx);
               if (ky < 0 || ky >= KT || kx < 0 || kx >= KT) continue;
-              acc[ph] = mfma<T>(w1[u0[ph]], b0, acc[ph]);
-              acc[ph] = mfma<T>(w1[u0[ph] + 1], b1, acc[ph]);
+              acc[ph] = mfma16x16x32<T>(w1[u0[ph]], b0, acc[ph]);
+              acc[ph] = mfma16x16x32<T>(w1[u0[ph] + 1], b1, acc[ph]);
               u0[ph] += 2;
             }
           }
@@ -1098,7 +1048,7 @@ __global__ __launch_bounds__(512, 2) void decoder3_kernel(D3Args a) {
           for (int ph = 0; ph < 4; ++ph) {
             const int ky = ky_of(ph >> 1, dy), kx = ky_of(ph & 1, dx);
             if (ky < 0 || ky >= KT || kx < 0 || kx >= KT) continue;
-            acc[ph] = mfma<T>(wt[u0[ph]++], b, acc[ph]);
+            acc[ph] = mfma16x16x32<T>(wt[u0[ph]++], b, acc[ph]);
           }
         }
       // map rows 2tl, 2tl + 1 as the Conv2D(1)'s B operands (zero below the image)
@@ -1111,9 +1061,9 @@ __global__ __launch_bounds__(512, 2) void decoder3_kernel(D3Args a) {
       }
 #pragma unroll
       for (int py = 0; py < 2; ++py) {
-        P0 = mfma<T>(wd[0][py], bv[py], P0);
-        P1 = mfma<T>(wd[1][py], bv[py], P1);
-        P2 = mfma<T>(wd[2][py], bv[py], P2);
+        P0 = mfma16x16x32<T>(wd[0][py], bv[py], P0);
+        P1 = mfma16x16x32<T>(wd[1][py], bv[py], P1);
+        P2 = mfma16x16x32<T>(wd[2][py], bv[py], P2);
       }
       E = P0;
       P0 = P1;
@@ -1417,20 +1367,21 @@ extern "C" int specenh_decoder3_ex(int dtype, const void* x, int N, int H, int W
   a.out_f16 = out_dtype == SPECENH_DTYPE_F16;
   hipStream_t st = (hipStream_t)stream;
   static LdsOptIn lds_map, lds_nm;  // with and without the map ring
-  (void)allow_lds(lds_map,
-                  {reinterpret_cast<const void*>(&decoder3_kernel<_Float16, true, 0>),
-                   reinterpret_cast<const void*>(&decoder3_kernel<__bf16, true, 0>)},
-                  d3::LDS_BYTES);
-  (void)allow_lds(lds_nm,
-                  {reinterpret_cast<const void*>(&decoder3_kernel<_Float16, false, 3>),
-                   reinterpret_cast<const void*>(&decoder3_kernel<__bf16, false, 3>),
-                   reinterpret_cast<const void*>(&decoder3_kernel<_Float16, false, 0>),
-                   reinterpret_cast<const void*>(&decoder3_kernel<__bf16, false, 0>),
-                   reinterpret_cast<const void*>(&decoder3_kernel<_Float16, false, 3, true>),
-                   reinterpret_cast<const void*>(&decoder3_kernel<__bf16, false, 3, true>),
-                   reinterpret_cast<const void*>(&decoder3_kernel<_Float16, false, 0, true>),
-                   reinterpret_cast<const void*>(&decoder3_kernel<__bf16, false, 0, true>)},
-                  d3::LDS_BYTES_NM);
+  if (allow_lds(lds_map,
+                {reinterpret_cast<const void*>(&decoder3_kernel<_Float16, true, 0>),
+                 reinterpret_cast<const void*>(&decoder3_kernel<__bf16, true, 0>)},
+                d3::LDS_BYTES) != hipSuccess ||
+      allow_lds(lds_nm,
+                {reinterpret_cast<const void*>(&decoder3_kernel<_Float16, false, 3>),
+                 reinterpret_cast<const void*>(&decoder3_kernel<__bf16, false, 3>),
+                 reinterpret_cast<const void*>(&decoder3_kernel<_Float16, false, 0>),
+                 reinterpret_cast<const void*>(&decoder3_kernel<__bf16, false, 0>),
+                 reinterpret_cast<const void*>(&decoder3_kernel<_Float16, false, 3, true>),
+                 reinterpret_cast<const void*>(&decoder3_kernel<__bf16, false, 3, true>),
+                 reinterpret_cast<const void*>(&decoder3_kernel<_Float16, false, 0, true>),
+                 reinterpret_cast<const void*>(&decoder3_kernel<__bf16, false, 0, true>)},
+                d3::LDS_BYTES_NM) != hipSuccess)
+    return set_error(SPECENH_EHIP, "decoder3: dynamic LDS attribute");
   // persistent: one workgroup per CU (256 VGPRs at 2 waves per SIMD; 68 KB of LDS, 120 KB with
   // the map ring)
   const unsigned grid = (unsigned)std::min<long long>(N, device_cus());
@@ -1438,32 +1389,23 @@ extern "C" int specenh_decoder3_ex(int dtype, const void* x, int N, int H, int W
   if (map && a.out_f16)
     return set_error(SPECENH_EUNSUPPORTED, "fused decoder: the map consumer stores fp32 only");
   const dim3 gd(grid), bd(512);
-  // the map-free kernels by (input dtype, output dtype) as a compile-time pair
-  auto launch_nm = [&](auto t, auto o16) {
-    using TT = decltype(t);
-    constexpr bool O16 = decltype(o16)::value;
-    if (short_lead)
-      SPECENH_LAUNCH((decoder3_kernel<TT, false, 0, O16>), gd, bd, d3::LDS_BYTES_NM, st, a);
-    else
-      SPECENH_LAUNCH((decoder3_kernel<TT, false, 3, O16>), gd, bd, d3::LDS_BYTES_NM, st, a);
-  };
-  using F16OUT = std::integral_constant<bool, true>;
-  using F32OUT = std::integral_constant<bool, false>;
-  if (dtype == SPECENH_DTYPE_F16) {
+  with_half_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    // the map-free kernels by output dtype as a compile-time flag
+    auto launch_nm = [&](auto o16) {
+      constexpr bool O16 = decltype(o16)::value;
+      if (short_lead)
+        SPECENH_LAUNCH((decoder3_kernel<T, false, 0, O16>), gd, bd, d3::LDS_BYTES_NM, st, a);
+      else
+        SPECENH_LAUNCH((decoder3_kernel<T, false, 3, O16>), gd, bd, d3::LDS_BYTES_NM, st, a);
+    };
     if (map)
-      SPECENH_LAUNCH((decoder3_kernel<_Float16, true, 0>), gd, bd, d3::LDS_BYTES, st, a);
+      SPECENH_LAUNCH((decoder3_kernel<T, true, 0>), gd, bd, d3::LDS_BYTES, st, a);
     else if (a.out_f16)
-      launch_nm(_Float16{}, F16OUT{});
+      launch_nm(std::true_type{});
     else
-      launch_nm(_Float16{}, F32OUT{});
-  } else {
-    if (map)
-      SPECENH_LAUNCH((decoder3_kernel<__bf16, true, 0>), gd, bd, d3::LDS_BYTES, st, a);
-    else if (a.out_f16)
-      launch_nm(__bf16{}, F16OUT{});
-    else
-      launch_nm(__bf16{}, F32OUT{});
-  }
+      launch_nm(std::false_type{});
+  });
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_error(SPECENH_EHIP, std::string("decoder3: ") + hipGetErrorString(e));
   return SPECENH_OK;

@@ -1,5 +1,5 @@
-// runtime.hip — error record, variant switches, per-device CU counts, LDS opt-in, last-launch
-// record (runtime.hpp).
+// runtime.hip — error record, variant switches, per-device CU counts and resident slots, LDS
+// opt-in, last-launch record (runtime.hpp).
 #include "runtime.hpp"
 
 #include <algorithm>
@@ -104,6 +104,24 @@ hipError_t allow_lds(LdsOptIn& site, std::initializer_list<const void*> kernels,
     if (e != hipSuccess) return e;
   }
   if (known) site.done[dev].store(true, std::memory_order_release);  // racing threads set the same
+  return hipSuccess;
+}
+
+hipError_t resident_slots(ResidentSlots& site, const void* kernel, int threads, int lds_bytes,
+                          long long* slots) {
+  static_assert(sizeof(site.per_cu) / sizeof(site.per_cu[0]) == kMaxDevices, "one count per device");
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  const bool known = dev >= 0 && dev < kMaxDevices;
+  int pc = known ? site.per_cu[dev].load(std::memory_order_relaxed) : 0;
+  if (pc == 0) {
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, kernel, threads, (size_t)lds_bytes);
+    if (e != hipSuccess) return e;
+    pc = std::max(1, pc);
+    if (known) site.per_cu[dev].store(pc, std::memory_order_relaxed);  // same value from any racing thread
+  }
+  *slots = (long long)pc * device_cus();
   return hipSuccess;
 }
 

@@ -1,6 +1,7 @@
 // runtime.hpp — host-side runtime shared by the kernel files: the error record, kernel-variant
-// switches, the per-device CU count for persistent grids, the opt-in to large dynamic LDS, and
-// the record of the last launched kernel.
+// switches, the per-device CU count and resident-workgroup slots for persistent grids
+// (device_cus, resident_slots), the opt-in to large dynamic LDS, the 16-bit type dispatcher
+// (with_half_type), and the record of the last launched kernel.
 //
 // Variant switches select between kernels that compute the same result (A/B tests and the
 // per-layer tools). They are read from the environment ONCE per process (SPECENH_<NAME>,
@@ -13,6 +14,8 @@
 #include <atomic>
 #include <initializer_list>
 #include <string>
+
+#include "specenh.h"
 
 namespace specenh {
 
@@ -86,6 +89,24 @@ struct LdsOptIn {
   std::atomic<bool> done[64];
 };
 hipError_t allow_lds(LdsOptIn& site, std::initializer_list<const void*> kernels, int bytes);
+
+// Grid of a persistent kernel: *slots = max(1, resident workgroups of `kernel` per CU at
+// `threads` and `lds_bytes` of dynamic LDS) x device_cus() on the calling thread's device. The
+// occupancy is queried once per device and call site (`site`: a zero-initialised static, one
+// per kernel instantiation); a later call is one hipGetDevice and one load. Call it after the
+// kernel's allow_lds.
+struct ResidentSlots {
+  std::atomic<int> per_cu[64];  // 0: not queried
+};
+hipError_t resident_slots(ResidentSlots& site, const void* kernel, int threads, int lds_bytes,
+                          long long* slots);
+
+// f(T{}) with T = _Float16 or __bf16 for the 16-bit dtype codes SPECENH_DTYPE_F16 / _BF16
+// (the caller has refused every other code)
+template <typename F>
+auto with_half_type(int dtype, F&& f) {
+  return dtype == SPECENH_DTYPE_F16 ? f(_Float16{}) : f(__bf16{});
+}
 
 // record `kernel` (the host stub a launch used) as the calling thread's last launch:
 // specenh_last_kernel_name() reports its symbol, so a measurement can key PMC counters by

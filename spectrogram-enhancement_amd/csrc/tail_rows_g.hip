@@ -34,6 +34,7 @@
 #include <string>
 
 #include "lds_dma.hpp"
+#include "mma.hpp"
 #include "specenh.h"
 #include "runtime.hpp"
 #include "wave.hpp"
@@ -45,44 +46,6 @@
 namespace specenh {
 
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-template <typename T>
-__device__ __forceinline__ f32x4 mfma(const uint4& a, const uint4& b, f32x4 acc) {
-  if constexpr (__is_same(T, _Float16))
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a),
-                                                  __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a),
-                                                   __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
-}
-
-template <typename T>
-__device__ __forceinline__ uint32_t pack2(float lo, float hi) {
-  const T a = (T)lo, b = (T)hi;
-  return (uint32_t)__builtin_bit_cast(unsigned short, a) |
-         ((uint32_t)__builtin_bit_cast(unsigned short, b) << 16);
-}
-
-// bias'd accumulators -> ReLU -> four T in 8 bytes (ReLU commutes with the rounding; fp16
-// runs it on the packed halves)
-template <typename T>
-__device__ __forceinline__ uint2 relu_pack(const f32x4& v) {
-  if constexpr (__is_same(T, _Float16)) {
-    const f16x2 lo = f16x2{(_Float16)v[0], (_Float16)v[1]};
-    const f16x2 hi = f16x2{(_Float16)v[2], (_Float16)v[3]};
-    const f16x2 z = f16x2{(_Float16)0.f, (_Float16)0.f};
-    return uint2{__builtin_bit_cast(uint32_t, __builtin_elementwise_max(lo, z)),
-                 __builtin_bit_cast(uint32_t, __builtin_elementwise_max(hi, z))};
-  } else {
-    return uint2{pack2<T>(fmaxf(v[0], 0.f), fmaxf(v[1], 0.f)),
-                 pack2<T>(fmaxf(v[2], 0.f), fmaxf(v[3], 0.f))};
-  }
-}
 
 constexpr int gcd_c(int a, int b) { return b ? gcd_c(b, a % b) : a; }
 constexpr int lcm_c(int a, int b) { return a / gcd_c(a, b) * b; }
@@ -379,7 +342,7 @@ __global__ __launch_bounds__((TG<CO, KT, KO>::THREADS)) void tailg_kernel(TGArgs
               if (!C::tap(ph0 + j, dy, dx)) continue;
 #pragma unroll
               for (int cb = 0; cb < CPW; ++cb)
-                acc[cb][j] = mfma<T>(wt[cb][C::tap_index(ph0 + j, dy, dx)], b, acc[cb][j]);
+                acc[cb][j] = mfma16x16x32<T>(wt[cb][C::tap_index(ph0 + j, dy, dx)], b, acc[cb][j]);
             }
           }
         }
@@ -425,7 +388,7 @@ __global__ __launch_bounds__((TG<CO, KT, KO>::THREADS)) void tailg_kernel(TGArgs
             uint4 bw;
             if constexpr (C::WO_LDS) bw = wol[(cbabs * P + p) * 64 + lane];
             else bw = wo[p][cb];
-            d = mfma<T>(av, bw, d);
+            d = mfma16x16x32<T>(av, bw, d);
           }
         }
         if (m < C::NSC)  // D[x' = 32 w + 16 blk + 4 kg + i][n = m]
