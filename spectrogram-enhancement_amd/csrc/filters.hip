@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "specenh.h"
+#include "filters_u8.hpp"
 #include "runtime.hpp"
 #include "wave.hpp"
 
@@ -209,15 +210,6 @@ struct GaussTaps {
   int kw, kh;
   unsigned short kx[MAX_TAPS], ky[MAX_TAPS];
 };
-
-__device__ __forceinline__ int reflect101(int p, int n) {
-  if (n == 1) return 0;
-  while (p < 0 || p >= n) {
-    if (p < 0) p = -p;
-    if (p >= n) p = 2 * n - 2 - p;
-  }
-  return p;
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void quant_u8_kernel(const T* S, long long batch, int rows,
@@ -419,6 +411,36 @@ int gauss_taps_q8(int n, double sigma, unsigned short* out) {
   return SPECENH_OK;
 }
 
+}  // namespace
+
+template <typename T>
+void launch_quant_u8(const T* S, long long batch, int rows, int cols, long long stride,
+                     double* stats, unsigned char* q, hipStream_t st) {
+  SPECENH_LAUNCH(stats_kernel<T>, dim3((unsigned)batch), dim3(256), 0, st, S, rows, cols,
+                     stride, (int)SPECENH_FILTER_RESCALE, (const double*)nullptr, stats);
+  SPECENH_LAUNCH(quant_u8_kernel<T>, dim3(grid_for(batch * rows * cols)), dim3(256), 0, st, S,
+                     batch, rows, cols, stride, stats, q);
+}
+
+template <typename T>
+void launch_rescale_u8(const unsigned char* u, long long batch, int rows, int cols,
+                       long long stride, double* stats, T* out, hipStream_t st) {
+  SPECENH_LAUNCH(u8_stats_kernel, dim3((unsigned)batch), dim3(256), 0, st, u, rows, cols, stats);
+  SPECENH_LAUNCH(u8_rescale_kernel<T>, dim3(grid_for(batch * rows * cols)), dim3(256), 0, st, u,
+                     batch, rows, cols, stride, stats, out);
+}
+
+template void launch_quant_u8<float>(const float*, long long, int, int, long long, double*,
+                                     unsigned char*, hipStream_t);
+template void launch_quant_u8<double>(const double*, long long, int, int, long long, double*,
+                                      unsigned char*, hipStream_t);
+template void launch_rescale_u8<float>(const unsigned char*, long long, int, int, long long,
+                                       double*, float*, hipStream_t);
+template void launch_rescale_u8<double>(const unsigned char*, long long, int, int, long long,
+                                        double*, double*, hipStream_t);
+
+namespace {
+
 struct U8Work {
   double* stats;
   unsigned char* a;
@@ -445,10 +467,7 @@ int run_u8_filter(bool gauss, const T* S, long long batch, int rows, int cols, l
   const long long n = batch * rows * cols;
   U8Work w = u8_work(ws, batch, n);
   const unsigned g = grid_for(n);
-  SPECENH_LAUNCH(stats_kernel<T>, dim3((unsigned)batch), dim3(256), 0, st, S, rows, cols,
-                     stride, (int)SPECENH_FILTER_RESCALE, (const double*)nullptr, w.stats);
-  SPECENH_LAUNCH(quant_u8_kernel<T>, dim3(g), dim3(256), 0, st, S, batch, rows, cols, stride,
-                     w.stats, w.a);
+  launch_quant_u8<T>(S, batch, rows, cols, stride, w.stats, w.a, st);
   if (gauss) {
     SPECENH_LAUNCH(gauss_rows_kernel, dim3(g), dim3(256), 0, st, w.a, batch, rows, cols, *tp,
                        w.h);
@@ -465,12 +484,11 @@ int run_u8_filter(bool gauss, const T* S, long long batch, int rows, int cols, l
                        1, 3, w.a);
     std::swap(w.a, w.b);
   }
-  SPECENH_LAUNCH(u8_stats_kernel, dim3((unsigned)batch), dim3(256), 0, st, w.b, rows, cols,
-                     w.stats);
-  SPECENH_LAUNCH(u8_rescale_kernel<T>, dim3(g), dim3(256), 0, st, w.b, batch, rows, cols,
-                     stride, w.stats, out);
+  launch_rescale_u8<T>(w.b, batch, rows, cols, stride, w.stats, out, st);
   return hipGetLastError() == hipSuccess ? SPECENH_OK : set_error(SPECENH_EHIP, "u8 filter launch");
 }
+
+}  // namespace
 
 int check_common(int dtype, const void* S, long long batch, int rows, int cols, long long stride,
                  const void* out) {
@@ -482,7 +500,6 @@ int check_common(int dtype, const void* S, long long batch, int rows, int cols, 
   return SPECENH_OK;
 }
 
-}  // namespace
 }  // namespace specenh
 
 using namespace specenh;

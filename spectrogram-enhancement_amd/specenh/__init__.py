@@ -1,7 +1,8 @@
 """specenh — MI355X-native spectrogram-enhancement hot path (gfx950, HIP via a C-ABI).
 
 Reference-compatible entry points (same names/arguments as the reference):
-  specenh.pipeline_data : specgr, norm, rescale, quantfilt, gaussblr, meansub, morph
+  specenh.pipeline_data : specgr, norm, rescale, quantfilt, gaussblr, meansub, morph, and
+                          bilateral (the denoiser of spec_denoising/dataset.ipynb)
   specenh.svd           : omega, denoiseSignal, computeSignal
   specenh.strips        : patch, unpatch, reshape
   specenh.keras         : layers / Model / compile / fit / predict / save / load_model

@@ -322,6 +322,22 @@ SIGNATURES_WAVELET_CROSS = {
                                                   _c.c_int]),
 }
 
+# bilateral label filter; must match include/specenh_bilateral.h
+BILATERAL_MAX_RADIUS = 15  # SPECENH_BILATERAL_MAX_RADIUS
+# SPECENH_BILATERAL_TILE_ROWS / _COLS: the output tile of one workgroup
+BILATERAL_TILE_ROWS, BILATERAL_TILE_COLS = 8, 128
+SIGNATURES_BILATERAL = {
+    "specenh_bilateral_taps": (_c.c_int, [_c.c_int, _c.c_double, _c.POINTER(_c.c_int),
+                                          _c.POINTER(_c.c_int)]),
+    "specenh_bilateral_u8": (_c.c_int, [_c.c_void_p, _c.c_longlong, _c.c_int, _c.c_int,
+                                        _c.c_longlong, _c.c_int, _c.c_double, _c.c_double,
+                                        _c.c_void_p, _c.c_void_p]),
+    "specenh_bilateral_workspace_bytes": (_c.c_size_t, [_c.c_longlong, _c.c_int, _c.c_int]),
+    "specenh_bilateral": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_longlong, _c.c_int, _c.c_int,
+                                     _c.c_longlong, _c.c_int, _c.c_double, _c.c_double,
+                                     _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+}
+
 
 def lib():
     """Load (once) and return the ctypes handle; raise ExtensionNotLoaded on failure."""
@@ -345,7 +361,8 @@ def lib():
                                   **SIGNATURES_MODES, **SIGNATURES_BISPECTRUM,
                                   **SIGNATURES_WAVENUMBER, **SIGNATURES_CORRELATION,
                                   **SIGNATURES_BEAMFORM, **SIGNATURES_WAVELET,
-                                  **SIGNATURES_WAVELET_CROSS}.items():
+                                  **SIGNATURES_WAVELET_CROSS,
+                                  **SIGNATURES_BILATERAL}.items():
             if dev_build and not hasattr(h, name):
                 continue  # an older revision's build for an A/B run (tools/build_rev_lib.sh)
             fn = getattr(h, name)

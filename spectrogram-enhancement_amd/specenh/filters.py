@@ -1,5 +1,6 @@
 """GPU label filters: norm / rescale / meansub / quantfilt / gaussblr / morph of
-spec_denoising/pipeline_data.py (:38-72) through ``torch.ops.specenh`` (csrc/filters.hip), and the
+spec_denoising/pipeline_data.py (:38-72) through ``torch.ops.specenh`` (csrc/filters.hip), the
+``bilateral`` denoiser of spec_denoising/dataset.ipynb (csrc/bilateral.hip), and the
 whole label chain of its main loop (:101-110) as ``label_pipeline``. The reference-named functions live in
 ``specenh.pipeline_data``; this module holds the device paths.
 
@@ -39,6 +40,9 @@ def _run(kind, t: torch.Tensor, arg):
         return ops.gaussblr(t, int(kw), int(kh), 0.0)
     if kind == "morph":
         return ops.morph(t)
+    if kind == "bilateral":
+        d, sigma_color, sigma_space = arg
+        return ops.bilateral(t, int(d), float(sigma_color), float(sigma_space))
     if kind == "quantfilt":
         return ops.quantfilt(t, float(arg))
     return ops.label_filter(t, int(arg))
@@ -102,6 +106,13 @@ def gaussblr(src, filt=(31, 3)):
 def morph(src):
     """pipeline_data.py:64-72: uint8 quantisation, MORPH_CLOSE 4x4 then MORPH_OPEN 3x1, rescale."""
     return _apply("morph", src, None, _image2d, lambda r, a: r)
+
+
+def bilateral(src, d=15, sigma_color=75, sigma_space=75):
+    """dataset.ipynb, bilateral(src): uint8 quantisation, cv2.bilateralFilter(u8, d, sigma_color,
+    sigma_space), rescale (csrc/bilateral.hip). The radius is d // 2, or round(1.5 sigma_space)
+    for d <= 0, and at most 15."""
+    return _apply("bilateral", src, (d, sigma_color, sigma_space), _image2d, lambda r, a: r)
 
 
 def label_pipeline(s, thr=0.9):

@@ -1758,6 +1758,64 @@ _op("gaussblr(Tensor S, int kw, int kh, float sigma) -> Tensor", _gaussblr,
 _op("morph(Tensor S) -> Tensor", _morph, lambda S: torch.empty_like(S))
 
 
+# ---------------------------------------------------------------- bilateral label filter
+def bilateral_taps(d, sigma_space):
+    """(radius, taps) cv2.bilateralFilter derives from ``(d, sigma_space)``
+    (specenh_bilateral_taps); NotImplementedError above radius 15."""
+    r, n = ctypes.c_int(0), ctypes.c_int(0)
+    _lib.check(_lib.lib().specenh_bilateral_taps(int(d), float(sigma_space), ctypes.byref(r),
+                                                 ctypes.byref(n)), "bilateral_taps")
+    return r.value, n.value
+
+
+def _bilateral_u8_check(img):
+    """(batch, rows, cols, batch stride) of uint8 images [B, rows, cols], each row-major; the
+    batch stride is free (>= rows * cols)."""
+    if img.dim() != 3 or img.dtype != torch.uint8:
+        raise ValueError("img must be uint8 [batch, rows, cols]")
+    B, rows, cols = img.shape
+    if rows < 1 or cols < 1:
+        raise ValueError("img must hold at least one row and one column")
+    if (cols > 1 and img.stride(2) != 1) or (rows > 1 and img.stride(1) != cols):
+        raise ValueError("every image of img must be row-major and contiguous")
+    stride = img.stride(0) if B > 1 else rows * cols
+    if stride < rows * cols:
+        raise ValueError("images must not overlap: batch stride >= rows * cols")
+    return B, rows, cols, stride
+
+
+def _bilateral_u8(img, d, sigma_color, sigma_space):
+    B, rows, cols, stride = _bilateral_u8_check(img)
+    out = torch.empty((B, rows, cols), dtype=torch.uint8, device=img.device)
+    _lib.check(_lib.lib().specenh_bilateral_u8(
+        _vp(img), B, rows, cols, stride, int(d), float(sigma_color), float(sigma_space),
+        _vp(out), _st(img)), "bilateral_u8")
+    return out
+
+
+def _bilateral_u8_fake(img, d, sigma_color, sigma_space):
+    B, rows, cols, _ = _bilateral_u8_check(img)
+    return img.new_empty((B, rows, cols), dtype=torch.uint8)
+
+
+def _bilateral(S, d, sigma_color, sigma_space):
+    B, rows, cols = _batch3(S)
+    L = _lib.lib()
+    out = torch.empty_like(S)
+    ws = torch.empty(max(16, int(L.specenh_bilateral_workspace_bytes(B, rows, cols))),
+                     dtype=torch.uint8, device=S.device)
+    _lib.check(L.specenh_bilateral(_code(S, (F32, F64)), _vp(S), B, rows, cols, rows * cols,
+                                   int(d), float(sigma_color), float(sigma_space), _vp(out),
+                                   _vp(ws), _st(S)), "bilateral")
+    return out
+
+
+_op("bilateral(Tensor S, int d, float sigma_color, float sigma_space) -> Tensor", _bilateral,
+    lambda S, d, sigma_color, sigma_space: torch.empty_like(S))
+_op("bilateral_u8(Tensor img, int d, float sigma_color, float sigma_space) -> Tensor",
+    _bilateral_u8, _bilateral_u8_fake)
+
+
 # ---------------------------------------------------------------- strip glue
 def _pack_out(S, rows, width, n_strips, out):
     if S.dim() != 3 or S.dtype != torch.float32 or S.stride(2) != 1 or S.stride(1) != S.shape[2]:

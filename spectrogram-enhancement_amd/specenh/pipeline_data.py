@@ -17,7 +17,8 @@ label-generator chain, run as HIP kernels too (csrc/filters.hip)
 numpy inputs come back as float64 numpy, device tensors stay on the device.
 ``gaussblr``/``morph`` restate OpenCV's GaussianBlur / MORPH_CLOSE+OPEN on the uint8
 quantisation (cv2 itself is absent here: their parity rests on that restatement and the
-filter goldens).
+filter goldens). ``bilateral``, the edge-preserving denoiser of
+spec_denoising/dataset.ipynb, restates cv2.bilateralFilter the same way (csrc/bilateral.hip).
 """
 from __future__ import annotations
 
@@ -116,6 +117,14 @@ def morph(src):
     """pipeline_data.py:64-72: uint8 quantisation -> MORPH_CLOSE 4x4 -> MORPH_OPEN 3x1 ->
     rescale, on the GPU (OpenCV's 8-bit algorithm restated; cv2 absent: parity unpinned)."""
     return _filters.morph(src)
+
+
+def bilateral(src, **kwargs):
+    """dataset.ipynb, bilateral(src): (rescale(src)*255).astype('uint8') ->
+    cv2.bilateralFilter(., 15, 75, 75) -> rescale, on the GPU (OpenCV's 8-bit algorithm restated;
+    cv2 absent: parity unpinned). Keywords ``d``, ``sigma_color``, ``sigma_space`` replace the
+    reference's 15, 75, 75."""
+    return _filters.bilateral(src, **kwargs)
 
 
 def label_pipeline(s, thr=0.9):
