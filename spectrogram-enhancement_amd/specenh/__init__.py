@@ -3,6 +3,7 @@
 Reference-compatible entry points (same names/arguments as the reference):
   specenh.pipeline_data : specgr, norm, rescale, quantfilt, gaussblr, meansub, morph, and
                           bilateral (the denoiser of spec_denoising/dataset.ipynb)
+  specenh.restoration   : denoise_nl_means (non-local means, for `from skimage import restoration`)
   specenh.svd           : omega, denoiseSignal, computeSignal
   specenh.strips        : patch, unpatch, reshape
   specenh.keras         : layers / Model / compile / fit / predict / save / load_model
@@ -42,6 +43,7 @@ first op call and its absence raises specenh._lib.ExtensionNotLoaded.
 __version__ = "0.2.0"
 
 from . import ops  # noqa: E402,F401  (registers torch.ops.specenh.*)
+from . import restoration  # noqa: E402,F401  (specenh.restoration.denoise_nl_means)
 
 
 def load_library():

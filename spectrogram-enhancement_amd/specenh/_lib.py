@@ -338,6 +338,17 @@ SIGNATURES_BILATERAL = {
                                      _c.c_void_p, _c.c_void_p, _c.c_void_p]),
 }
 
+# non-local means denoising; must match include/specenh_nlmeans.h
+NLMEANS_MAX_PATCH = 9  # SPECENH_NLMEANS_MAX_PATCH
+NLMEANS_MAX_DISTANCE = 15  # SPECENH_NLMEANS_MAX_DISTANCE
+# SPECENH_NLMEANS_TILE_ROWS / _COLS: the output tile of one workgroup
+NLMEANS_TILE_ROWS, NLMEANS_TILE_COLS = 16, 64
+SIGNATURES_NLMEANS = {
+    "specenh_nlmeans": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_longlong, _c.c_int, _c.c_int,
+                                   _c.c_longlong, _c.c_int, _c.c_int, _c.c_double, _c.c_double,
+                                   _c.c_void_p, _c.c_void_p]),
+}
+
 
 def lib():
     """Load (once) and return the ctypes handle; raise ExtensionNotLoaded on failure."""
@@ -362,7 +373,7 @@ def lib():
                                   **SIGNATURES_WAVENUMBER, **SIGNATURES_CORRELATION,
                                   **SIGNATURES_BEAMFORM, **SIGNATURES_WAVELET,
                                   **SIGNATURES_WAVELET_CROSS,
-                                  **SIGNATURES_BILATERAL}.items():
+                                  **SIGNATURES_BILATERAL, **SIGNATURES_NLMEANS}.items():
             if dev_build and not hasattr(h, name):
                 continue  # an older revision's build for an A/B run (tools/build_rev_lib.sh)
             fn = getattr(h, name)

@@ -1,6 +1,7 @@
 """GPU label filters: norm / rescale / meansub / quantfilt / gaussblr / morph of
 spec_denoising/pipeline_data.py (:38-72) through ``torch.ops.specenh`` (csrc/filters.hip), the
-``bilateral`` denoiser of spec_denoising/dataset.ipynb (csrc/bilateral.hip), and the
+``bilateral`` denoiser of spec_denoising/dataset.ipynb (csrc/bilateral.hip), non-local means
+(``nl_means``, csrc/nlmeans.hip; ``specenh.restoration`` has the scikit-image name), and the
 whole label chain of its main loop (:101-110) as ``label_pipeline``. The reference-named functions live in
 ``specenh.pipeline_data``; this module holds the device paths.
 
@@ -12,6 +13,8 @@ N-D numpy inputs keep the reference's whole-array semantics: norm / rescale over
 elements, quantfilt per column of axis 0, meansub over axis 1 with one global rescale.
 """
 from __future__ import annotations
+
+import operator
 
 import numpy as np
 import torch
@@ -43,6 +46,9 @@ def _run(kind, t: torch.Tensor, arg):
     if kind == "bilateral":
         d, sigma_color, sigma_space = arg
         return ops.bilateral(t, int(d), float(sigma_color), float(sigma_space))
+    if kind == "nl_means":
+        patch_size, patch_distance, h, sigma = arg
+        return ops.nl_means(t, int(patch_size), int(patch_distance), float(h), float(sigma))
     if kind == "quantfilt":
         return ops.quantfilt(t, float(arg))
     return ops.label_filter(t, int(arg))
@@ -113,6 +119,23 @@ def bilateral(src, d=15, sigma_color=75, sigma_space=75):
     sigma_space), rescale (csrc/bilateral.hip). The radius is d // 2, or round(1.5 sigma_space)
     for d <= 0, and at most 15."""
     return _apply("bilateral", src, (d, sigma_color, sigma_space), _image2d, lambda r, a: r)
+
+
+def nl_means(src, patch_size=7, patch_distance=11, h=0.1, sigma=0.0):
+    """Non-local means with skimage.restoration.denoise_nl_means's fast_mode weighting
+    (csrc/nlmeans.hip; include/specenh_nlmeans.h has the arithmetic): every pixel becomes the
+    mean of the (2 patch_distance + 1)^2 pixels around it, each weighted by
+    exp(-max(d2 - 2 sigma^2, 0) / h^2), d2 the mean squared difference of the two
+    patch_size x patch_size patches; no rescale, fp32 arithmetic. patch_size is odd and at most
+    9, patch_distance at most 15; both are integers (a float is a TypeError, not truncated)."""
+    def to2d(a):
+        if a.ndim != 2:
+            raise ValueError("nl_means takes one 2-D image (or a [batch, rows, cols] device "
+                             "tensor)")
+        return a
+
+    arg = (operator.index(patch_size), operator.index(patch_distance), h, sigma)
+    return _apply("nl_means", src, arg, to2d, lambda r, a: r)
 
 
 def label_pipeline(s, thr=0.9):

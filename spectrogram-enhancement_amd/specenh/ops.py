@@ -1816,6 +1816,34 @@ _op("bilateral_u8(Tensor img, int d, float sigma_color, float sigma_space) -> Te
     _bilateral_u8, _bilateral_u8_fake)
 
 
+# ---------------------------------------------------------------- non-local means
+def _nl_means_shape(S):
+    if S.dim() not in (2, 3):
+        raise ValueError("S must be [rows, cols] or [batch, rows, cols]")
+    if S.shape[-2] < 1 or S.shape[-1] < 1:
+        raise ValueError("S must hold at least one row and one column")
+
+
+def _nl_means(S, patch_size, patch_distance, h, sigma):
+    _nl_means_shape(S)
+    S3 = (S if S.dim() == 3 else S.unsqueeze(0)).contiguous()
+    B, rows, cols = S3.shape
+    out = torch.empty_like(S3)
+    _lib.check(_lib.lib().specenh_nlmeans(_code(S3, (F32, F64)), _vp(S3), B, rows, cols,
+                                          rows * cols, int(patch_size), int(patch_distance),
+                                          float(h), float(sigma), _vp(out), _st(S3)), "nl_means")
+    return out.view(S.shape)
+
+
+def _nl_means_fake(S, patch_size, patch_distance, h, sigma):
+    _nl_means_shape(S)
+    return S.new_empty(S.shape)
+
+
+_op("nl_means(Tensor S, int patch_size, int patch_distance, float h, float sigma) -> Tensor",
+    _nl_means, _nl_means_fake)
+
+
 # ---------------------------------------------------------------- strip glue
 def _pack_out(S, rows, width, n_strips, out):
     if S.dim() != 3 or S.dtype != torch.float32 or S.stride(2) != 1 or S.stride(1) != S.shape[2]:

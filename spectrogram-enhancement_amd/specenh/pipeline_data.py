@@ -19,6 +19,8 @@ numpy inputs come back as float64 numpy, device tensors stay on the device.
 quantisation (cv2 itself is absent here: their parity rests on that restatement and the
 filter goldens). ``bilateral``, the edge-preserving denoiser of
 spec_denoising/dataset.ipynb, restates cv2.bilateralFilter the same way (csrc/bilateral.hip).
+The reference's other import, ``from skimage import restoration`` (:21), has its counterpart in
+``specenh.restoration`` (non-local means, csrc/nlmeans.hip).
 """
 from __future__ import annotations
 
