@@ -4,6 +4,8 @@ Reference-compatible entry points (same names/arguments as the reference):
   specenh.pipeline_data : specgr, norm, rescale, quantfilt, gaussblr, meansub, morph, and
                           bilateral (the denoiser of spec_denoising/dataset.ipynb)
   specenh.restoration   : denoise_nl_means (non-local means, for `from skimage import restoration`)
+  specenh.cluster       : KMeans (for `from sklearn.cluster import KMeans`), batched kmeans,
+                          segment (pixel k-means: a data-driven mode / background mask)
   specenh.svd           : omega, denoiseSignal, computeSignal
   specenh.strips        : patch, unpatch, reshape
   specenh.keras         : layers / Model / compile / fit / predict / save / load_model
@@ -44,6 +46,7 @@ __version__ = "0.2.0"
 
 from . import ops  # noqa: E402,F401  (registers torch.ops.specenh.*)
 from . import restoration  # noqa: E402,F401  (specenh.restoration.denoise_nl_means)
+from . import cluster  # noqa: E402,F401  (specenh.cluster.KMeans)
 
 
 def load_library():

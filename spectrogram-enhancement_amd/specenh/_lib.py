@@ -349,6 +349,24 @@ SIGNATURES_NLMEANS = {
                                    _c.c_void_p, _c.c_void_p]),
 }
 
+# k-means clustering; must match include/specenh_kmeans.h
+KMEANS_MAX_K = 256  # SPECENH_KMEANS_MAX_K
+KMEANS_MAX_D = 65536  # SPECENH_KMEANS_MAX_D
+# SPECENH_KMEANS_TILE / _CHUNK / _SLAB: points of a workgroup, d of a chunk of the dot
+# products, points of a slab of the update (the rounding counts c_s and c_u follow from them)
+KMEANS_TILE, KMEANS_CHUNK, KMEANS_SLAB = 64, 32, 1024
+SIGNATURES_KMEANS = {
+    "specenh_kmeans_workspace_bytes": (_c.c_size_t, [_c.c_longlong, _c.c_longlong, _c.c_int,
+                                                     _c.c_int]),
+    "specenh_kmeans_assign": (_c.c_int, [_c.c_void_p, _c.c_longlong, _c.c_longlong, _c.c_int,
+                                         _c.c_longlong, _c.c_longlong, _c.c_void_p, _c.c_int,
+                                         _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "specenh_kmeans_step": (_c.c_int, [_c.c_void_p, _c.c_longlong, _c.c_longlong, _c.c_int,
+                                       _c.c_longlong, _c.c_longlong, _c.c_void_p, _c.c_int,
+                                       _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                       _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+}
+
 
 def lib():
     """Load (once) and return the ctypes handle; raise ExtensionNotLoaded on failure."""
@@ -373,7 +391,8 @@ def lib():
                                   **SIGNATURES_WAVENUMBER, **SIGNATURES_CORRELATION,
                                   **SIGNATURES_BEAMFORM, **SIGNATURES_WAVELET,
                                   **SIGNATURES_WAVELET_CROSS,
-                                  **SIGNATURES_BILATERAL, **SIGNATURES_NLMEANS}.items():
+                                  **SIGNATURES_BILATERAL, **SIGNATURES_NLMEANS,
+                                  **SIGNATURES_KMEANS}.items():
             if dev_build and not hasattr(h, name):
                 continue  # an older revision's build for an A/B run (tools/build_rev_lib.sh)
             fn = getattr(h, name)

@@ -1844,6 +1844,85 @@ _op("nl_means(Tensor S, int patch_size, int patch_distance, float h, float sigma
     _nl_means, _nl_means_fake)
 
 
+# ---------------------------------------------------------------- k-means
+def _kmeans_shape(X, C):
+    """(batch, n, d, k) of points X [n, d] or [batch, n, d] and centres C [k, d] or [batch, k, d]."""
+    if X.dim() not in (2, 3) or C.dim() != X.dim():
+        raise ValueError("X must be [n, d] or [batch, n, d] and C [k, d] or [batch, k, d]")
+    if X.dtype != torch.float32 or C.dtype != torch.float32:
+        raise TypeError("X and C must be float32")
+    n, d = X.shape[-2:]
+    k = C.shape[-2]
+    if C.shape[-1] != d or (X.dim() == 3 and C.shape[0] != X.shape[0]):
+        raise ValueError("C must have X's batch and d")
+    if n < 1 or d < 1 or k < 1:
+        raise ValueError("X and C must hold at least one row and one column")
+    return (X.shape[0] if X.dim() == 3 else 1), n, d, k
+
+
+def _kmeans_layout(X3):
+    """X3 as the kernels read it, (X3, ld, batch stride): unit stride along d, rows ld >= d
+    apart, items at least n * ld apart; any other view is copied."""
+    B, n, d = X3.shape
+    ld = X3.stride(1) if n > 1 else d
+    stride = X3.stride(0) if B > 1 else n * ld
+    if (d > 1 and X3.stride(2) != 1) or ld < d or stride < n * ld:
+        return X3.contiguous(), d, n * d
+    return X3, ld, stride
+
+
+def _kmeans_ws(L, B, n, d, k, device):
+    return torch.empty(max(16, int(L.specenh_kmeans_workspace_bytes(B, n, d, k))),
+                       dtype=torch.uint8, device=device)
+
+
+def _kmeans_assign(X, C):
+    B, n, d, k = _kmeans_shape(X, C)
+    X3, ld, stride = _kmeans_layout(X.reshape(B, n, d) if X.dim() == 2 else X)
+    C3 = C.reshape(B, k, d).contiguous()
+    L = _lib.lib()
+    labels = torch.empty((B, n), dtype=torch.int32, device=X.device)
+    ws = _kmeans_ws(L, B, n, d, k, X.device)
+    _lib.check(L.specenh_kmeans_assign(_vp(X3), B, n, d, ld, stride, _vp(C3), k, _vp(labels),
+                                       _vp(ws), ws.numel(), _st(X3)), "kmeans_assign")
+    return labels if X.dim() == 3 else labels.view(n)
+
+
+def _kmeans_assign_fake(X, C):
+    _kmeans_shape(X, C)
+    return X.new_empty(X.shape[:-1], dtype=torch.int32)
+
+
+def _kmeans_step(X, C):
+    B, n, d, k = _kmeans_shape(X, C)
+    X3, ld, stride = _kmeans_layout(X.reshape(B, n, d) if X.dim() == 2 else X)
+    C3 = C.reshape(B, k, d).contiguous()
+    L = _lib.lib()
+    labels = torch.empty((B, n), dtype=torch.int32, device=X.device)
+    C_new = torch.empty_like(C3)
+    counts = torch.empty((B, k), dtype=torch.int32, device=X.device)
+    inertia = torch.empty((B,), dtype=torch.float32, device=X.device)
+    ws = _kmeans_ws(L, B, n, d, k, X.device)
+    _lib.check(L.specenh_kmeans_step(_vp(X3), B, n, d, ld, stride, _vp(C3), k, _vp(labels),
+                                     _vp(C_new), _vp(counts), _vp(inertia), _vp(ws), ws.numel(),
+                                     _st(X3)), "kmeans_step")
+    if X.dim() == 3:
+        return labels, C_new, counts, inertia
+    return labels.view(n), C_new.view(k, d), counts.view(k), inertia.view(())
+
+
+def _kmeans_step_fake(X, C):
+    _kmeans_shape(X, C)
+    lead = X.shape[:-2]
+    return (X.new_empty(X.shape[:-1], dtype=torch.int32), C.new_empty(C.shape),
+            X.new_empty(C.shape[:-1], dtype=torch.int32), X.new_empty(lead))
+
+
+_op("kmeans_assign(Tensor X, Tensor C) -> Tensor", _kmeans_assign, _kmeans_assign_fake)
+_op("kmeans_step(Tensor X, Tensor C) -> (Tensor, Tensor, Tensor, Tensor)", _kmeans_step,
+    _kmeans_step_fake)
+
+
 # ---------------------------------------------------------------- strip glue
 def _pack_out(S, rows, width, n_strips, out):
     if S.dim() != 3 or S.dtype != torch.float32 or S.stride(2) != 1 or S.stride(1) != S.shape[2]:

@@ -20,7 +20,9 @@ quantisation (cv2 itself is absent here: their parity rests on that restatement 
 filter goldens). ``bilateral``, the edge-preserving denoiser of
 spec_denoising/dataset.ipynb, restates cv2.bilateralFilter the same way (csrc/bilateral.hip).
 The reference's other import, ``from skimage import restoration`` (:21), has its counterpart in
-``specenh.restoration`` (non-local means, csrc/nlmeans.hip).
+``specenh.restoration`` (non-local means, csrc/nlmeans.hip), and ``from sklearn.cluster import
+KMeans`` (:19) in ``specenh.cluster`` (csrc/kmeans.hip; ``cluster.segment`` is the data-driven
+alternative to ``quantfilt``'s fixed quantile).
 """
 from __future__ import annotations
 
