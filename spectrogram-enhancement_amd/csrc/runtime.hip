@@ -31,7 +31,7 @@ constexpr VariantName kVariants[V_COUNT] = {
     {"SVD_RECON_BLOCKS", 0}, {"CONVT_PG", 0}, {"SVD_GZ_ROWS", 0}, {"EIG_SPLIT", 0}, {"CO1_VALU", 0},
     {"C1_MASK_MFMA", 1}, {"S2_MIN_NT", 2}, {"PATCH_MIN_WG", 512}, {"WGRAD_WG", 1024}, {"WGRAD_C1_TILES", 4},
     {"EIG_GRID", 32}, {"ROWS_BANDS", -1}, {"CONVT_STORE8", 0},
-    {"CONV_ROWS_SCHED", 1}, {"ENC2_SCHED", 1},
+    {"CONV_ROWS_SCHED", 1}, {"ENC2_SCHED", 1}, {"SVD_TOP1_LDS", 0},
 };
 
 std::atomic<int> g_variant[V_COUNT];

@@ -71,6 +71,7 @@ enum Variant : int {
   V_CONVT_STORE8,     // convT1 row sweep: per-wave rings + 8-byte stores (rounds 4-6) instead of staged whole-line stores
   V_CONV_ROWS_SCHED,  // conv3 + pool row sweep: 1 (default) fragments one step ahead and the pool under the MFMAs, 0 the round 4-6 step
   V_ENC2_SCHED,       // fused encoder (two workgroups per CU): 1 (default) flag-word step bookkeeping, staged whole-line pooled stores and the packed pool, 0 the round 4-7 step
+  V_SVD_TOP1_LDS,     // top-1 complement: top1_kernel (X in LDS, two workgroups per CU) in both orientations instead of top1_kernel_reg (X in registers, four) where rows are contiguous
   V_COUNT
 };
 

@@ -1865,6 +1865,12 @@ __device__ __forceinline__ int xz_chunk(int g, int j) {
 }
 // X | Zt (4 x ZP, basis transposed) | U (N x 4) | part (4 waves x N x 4) | reduction scratch
 constexpr size_t LDS_BYTES = (size_t)N * LD * 4 + 4 * ZP * 4 + N * 4 * 4 + 4 * N * 4 * 4 + 64 * 8;
+// top1_kernel_reg (X in registers) keeps U with 4 pad words after every 16 rows: its X Z
+// phase writes rows a + 16 m from the 16 lanes of one a, which share 4 banks at pitch 4.
+__host__ __device__ constexpr int uoff(int k) { return 4 * (k + (k >> 4)); }
+constexpr int UW = uoff(N);  // words
+// Zt | U (padded) | part (4 waves x N x 4) | reduction scratch
+constexpr size_t REG_LDS_BYTES = 4 * ZP * 4 + UW * 4 + 4 * N * 4 * 4 + 64 * 8;
 
 // 4 x 4 Cholesky M = L L^T (lower) in fp64, returned as the strictly lower part of L and
 // rinv = 1 / diag(L). A pivot below 1e-20 of its diagonal entry marks the column dead (its
@@ -1949,8 +1955,8 @@ __device__ __forceinline__ void jacobi4(float (&A)[4][4], float (&Q)[4][4]) {
 // Sum NV doubles over the 128 threads of waves 0 and 1 (waves 2, 3 skip the wave sums);
 // every thread returns the totals. One barrier; the caller separates reuse of sR.
 template <int NV>
-__device__ __forceinline__ void bsum128(double (&v)[NV], double* sR) {
-  const int tid = threadIdx.x, w = tid >> 6;
+__device__ __forceinline__ void bsum128(double (&v)[NV], double* sR, int tid = threadIdx.x) {
+  const int w = tid >> 6;
   if (w < 2) {
 #pragma unroll
     for (int j = 0; j < NV; ++j) v[j] = wave_sum_dpp(v[j]);
@@ -1969,11 +1975,12 @@ __device__ __forceinline__ void bsum128(double (&v)[NV], double* sR) {
 // thread returns all NV sums. Y and U are row-major N x 4, Z transposed (4 x ZP). With
 // SPECENH_TOP1_SWZ thread c takes rows 8 i + c (the 8 lanes of one j on 8 banks); the
 // contiguous 16-row chunks (rows 16 c + i) put them on ONE bank of the row-major blocks
-// (8-way: 1,936 of 2,192 LDS cycles of a check round, tools/lds_banks.py).
-template <int NV>
+// (8-way: 1,936 of 2,192 LDS cycles of a check round, tools/lds_banks.py). UP: U rows at
+// uoff(row) (top1_kernel_reg) instead of pitch 4.
+template <int NV, bool UP = false>
 __device__ __forceinline__ void gram_sums(const float* sY, const float* sZt, const float* sU,
-                                          double* sRed) {
-  const int t = threadIdx.x, j = t >> 3, c = t & 7;
+                                          double* sRed, int t = threadIdx.x) {
+  const int j = t >> 3, c = t & 7;
   double s = 0.0;
   if (j < NV) {
     const int n = j % 10, src = j / 10;
@@ -1982,8 +1989,9 @@ __device__ __forceinline__ void gram_sums(const float* sY, const float* sZt, con
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int row = SPECENH_TOP1_SWZ ? 8 * i + c : 16 * c + i;
-      const float va = src == 0 ? sY[4 * row + a] : (src == 1 ? sZt[zt(a, row)] : sU[4 * row + a]);
-      const float vb = src == 0 ? sY[4 * row + b] : (src == 1 ? sZt[zt(b, row)] : sU[4 * row + b]);
+      const int ur = UP ? uoff(row) : 4 * row;
+      const float va = src == 0 ? sY[4 * row + a] : (src == 1 ? sZt[zt(a, row)] : sU[ur + a]);
+      const float vb = src == 0 ? sY[4 * row + b] : (src == 1 ? sZt[zt(b, row)] : sU[ur + b]);
       s = fma((double)va, (double)vb, s);
     }
   }
@@ -2372,6 +2380,468 @@ __global__ __launch_bounds__(256, 2) void top1_kernel(XView x, int Kr, int r, fl
 #pragma unroll
       for (int c = 0; c < 4; ++c)
         o[c] = to_out<TO>((float)fma(-ud[k + c], vi, (double)sX[(k + c) * LD + i]));
+    }
+  }
+  T1_MARK(6);
+#ifdef SPECENH_TOP1_STATS
+  if (phase_clk && tid == 0)
+    for (int q = 0; q < 8; ++q) phase_clk[b * 8 + q] = tacc[q];
+#endif
+#undef T1_MARK
+}
+
+// ---------------------------------------------------------------- 2''. top-1, X in registers
+// top1_kernel step for step (same start block, rounds, checks, fp64 step, output and flag
+// word) for the orientation with contiguous rows of X and of the output, with the padded
+// 128 x 128 X held in registers instead of LDS: 13 KB of LDS and at most 128 VGPRs, so four
+// workgroups share a CU instead of two. Thread (a = tid >> 4, c = tid & 15) owns rows
+// a + 16 m (m < 8) of the float4 column chunks c and c + 16; a 16-lane DPP row (one a) covers
+// 256 contiguous bytes of a row of X per chunk. Only who reduces what changes:
+//   U = X Z    partial sums over the thread's 8 columns, reduce-scatter over the 16 lanes of
+//              the DPP row (lane c ends with row a + 16 (c >> 1), columns 2 (c & 1) + {0, 1});
+//   Y = X^T U  partial sums over the thread's 8 rows, reduce-scatter over the wave's four a
+//              (lane bits 5 and 4: v_permlane32_swap, v_permlane16_swap), then the four
+//              waves' partial sums meet in LDS as in top1_kernel;
+//   fp64 step and output: the same two reductions in double, X from the registers.
+namespace top1 {
+// One reduce-scatter step between the lanes that DPP control CTRL pairs (an involution that
+// flips the lane bit behind `up`): the lane keeps `hi` if `up`, else `lo`, and adds the
+// partner's copy of the same.
+template <int CTRL, typename T>
+__device__ __forceinline__ T rs_dpp(bool up, T lo, T hi) {
+  const T keep = up ? hi : lo, send = up ? lo : hi;
+  return keep + dpp<CTRL, false>(send);
+}
+// The same step across lane bit 5 (v_permlane32_swap: lanes 32-63 of the first operand trade
+// with lanes 0-31 of the second) and lane bit 4 (v_permlane16_swap: odd rows of the first with
+// even rows of the second): the lane with the bit set keeps `hi`. No selects: after the swap
+// both operands hold the kept half, the lane's own and its partner's.
+__device__ __forceinline__ float rs_swap32(float lo, float hi) {
+  const auto s = __builtin_amdgcn_permlane32_swap(__float_as_uint(lo), __float_as_uint(hi), false, false);
+  return __uint_as_float(s[0]) + __uint_as_float(s[1]);
+}
+__device__ __forceinline__ float rs_swap16(float lo, float hi) {
+  const auto s = __builtin_amdgcn_permlane16_swap(__float_as_uint(lo), __float_as_uint(hi), false, false);
+  return __uint_as_float(s[0]) + __uint_as_float(s[1]);
+}
+__device__ __forceinline__ double rs_swap32(double lo, double hi) {
+  const unsigned long long l = __double_as_longlong(lo), h = __double_as_longlong(hi);
+  const auto s0 = __builtin_amdgcn_permlane32_swap((unsigned)l, (unsigned)h, false, false);
+  const auto s1 = __builtin_amdgcn_permlane32_swap((unsigned)(l >> 32), (unsigned)(h >> 32), false, false);
+  return __longlong_as_double(((unsigned long long)s1[0] << 32) | s0[0]) +
+         __longlong_as_double(((unsigned long long)s1[1] << 32) | s0[1]);
+}
+__device__ __forceinline__ double rs_swap16(double lo, double hi) {
+  const unsigned long long l = __double_as_longlong(lo), h = __double_as_longlong(hi);
+  const auto s0 = __builtin_amdgcn_permlane16_swap((unsigned)l, (unsigned)h, false, false);
+  const auto s1 = __builtin_amdgcn_permlane16_swap((unsigned)(l >> 32), (unsigned)(h >> 32), false, false);
+  return __longlong_as_double(((unsigned long long)s1[0] << 32) | s0[0]) +
+         __longlong_as_double(((unsigned long long)s1[1] << 32) | s0[1]);
+}
+// four outputs as one 16-byte (fp32) or 8-byte (16-bit types) store
+template <typename TO>
+struct alignas(4 * sizeof(TO)) Out4 {
+  TO v[4];
+};
+}  // namespace top1
+#ifndef SPECENH_TOP1_REG_WGS
+#define SPECENH_TOP1_REG_WGS 4  // workgroups per CU the register budget is cut for (128 VGPRs)
+#endif
+
+template <typename TO>
+__global__ __launch_bounds__(256, SPECENH_TOP1_REG_WGS) void top1_kernel_reg(XView x, int Kr, int r, float tolv,
+                                                           int* flags, TO* out, long long ob,
+                                                           long long osk, long long batch,
+                                                           long long* phase_clk) {
+  using namespace top1;
+#ifdef SPECENH_TOP1_STATS  // development build: shader clocks per phase (thread 0)
+  long long tacc[8], tlast;
+#define T1_MARK(slot)                                      \
+  do {                                                     \
+    const long long now_ = __builtin_amdgcn_s_memtime();   \
+    tacc[slot] += now_ - tlast;                            \
+    tlast = now_;                                          \
+  } while (0)
+#else
+#define T1_MARK(slot) \
+  do {                \
+  } while (0)
+#endif
+  __shared__ __attribute__((aligned(16))) unsigned char smem[REG_LDS_BYTES];
+  float* sZt = reinterpret_cast<float*>(smem);          // 4 x ZP
+  float* sU = sZt + 4 * ZP;                             // N rows of 4 at uoff(k)
+  float* sP = sU + UW;                                  // 4 x N x 4
+  double* sR = reinterpret_cast<double*>(sP + 16 * N);  // 64
+  double* vd = reinterpret_cast<double*>(sP);  // N: final v (fp64), after the iteration
+  double* ud = vd + N;                            // N: u = X v
+  double* wd = ud + N;                            // 4 x N: the waves' partial sums of X^T u
+  int tid = threadIdx.x, lane, w, a, c, i0;
+  bool c3, c2, c1, c0;
+  auto lane_map = [&]() {
+    lane = tid & 63, w = tid >> 6, a = tid >> 4, c = tid & 15;
+    c3 = c & 8, c2 = c & 4, c1 = c & 2, c0 = c & 1;
+    // the two columns the lane keeps after the reduce-scatter over the wave's four a
+    i0 = 64 * (lane >> 5) + 4 * c + 2 * ((lane >> 4) & 1);
+  };
+  lane_map();
+  // The lane map and the LDS addresses that follow from it are worked out again in every
+  // phase of a round (a few dozen integer operations): hoisted out of the loop, or held from
+  // one phase to the next, they are up to 40 more registers, which the 128-register budget
+  // turns into spills.
+  auto fresh_map = [&]() {
+    asm volatile("" : "+v"(tid));
+    lane_map();
+  };
+#ifdef SPECENH_TOP1_STATS
+  for (int q = 0; q < 8; ++q) tacc[q] = 0;
+  tlast = __builtin_amdgcn_s_memtime();
+#endif
+  const long long b = blockIdx.x;
+  if (b >= batch) return;
+  const float* X = x.base + b * x.batch_stride;
+
+  // ---- X into registers (zero-padded): 16-byte loads along i, all in flight
+  float4 xr[8][2];
+#pragma unroll
+  for (int m = 0; m < 8; ++m)
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int k = a + 16 * m, i = 4 * c + 64 * h;
+      xr[m][h] = (k < Kr && i < r) ? *reinterpret_cast<const float4*>(X + (long long)k * x.sk + i)
+                                   : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  // The fp64 phases each convert X again: held as doubles it would be 128 more registers
+  // (the compiler shares the conversions between the phases and spills them). The empty asm
+  // makes the registers opaque, so nothing computed from X is carried past it.
+  auto pin_x = [&]() {
+#pragma unroll
+    for (int m = 0; m < 8; ++m)
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+        asm volatile("" : "+v"(xr[m][h].x), "+v"(xr[m][h].y), "+v"(xr[m][h].z), "+v"(xr[m][h].w));
+  };
+  if (tid < N)
+#pragma unroll
+    for (int p = 0; p < 4; ++p)  // the start block of top1_kernel
+      sZt[zt(p, tid)] = tid < r ? (p == 0 ? 1.f : hash_unit(tid, p)) : 0.f;
+  lds_barrier();  // the basis; X is still in flight
+  T1_MARK(0);
+
+  for (int t = 1;; ++t) {
+    fresh_map();
+    {  // U = X Z
+      float acc[32];  // [m][p]
+#pragma unroll
+      for (int q = 0; q < 32; ++q) acc[q] = 0.f;
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {  // one basis vector's chunk at a time (4 registers)
+          const float4 zv = *reinterpret_cast<const float4*>(sZt + zt(p, 4 * c + 64 * h));
+#pragma unroll
+          for (int m = 0; m < 8; ++m) {
+            const float4 xv = xr[m][h];
+            float s = acc[4 * m + p];
+            s = fmaf(xv.x, zv.x, s);
+            s = fmaf(xv.y, zv.y, s);
+            s = fmaf(xv.z, zv.z, s);
+            s = fmaf(xv.w, zv.w, s);
+            acc[4 * m + p] = s;
+          }
+        }
+      // reduce-scatter over the 16 column chunks of the DPP row (lane bits 3, 2, 1, 0): the
+      // lane keeps row m = c >> 1, columns p = 2 (c & 1) + {0, 1}
+      float a16[16], a8[8], a4[4], a2[2];
+      fresh_map();
+#pragma unroll
+      for (int q = 0; q < 16; ++q) a16[q] = rs_dpp<0x128>(c3, acc[q], acc[16 + q]);  // row_ror:8
+#pragma unroll
+      for (int q = 0; q < 8; ++q) a8[q] = rs_dpp<0x141>(c2, a16[q], a16[8 + q]);  // row_half_mirror
+#pragma unroll
+      for (int q = 0; q < 4; ++q) a4[q] = rs_dpp<0x4E>(c1, a8[q], a8[4 + q]);  // quad_perm [2, 3, 0, 1]
+#pragma unroll
+      for (int q = 0; q < 2; ++q) a2[q] = rs_dpp<0xB1>(c0, a4[q], a4[2 + q]);  // quad_perm [1, 0, 3, 2]
+      *reinterpret_cast<float2*>(sU + uoff(a + 16 * (c >> 1)) + 2 * (c & 1)) = make_float2(a2[0], a2[1]);
+    }
+    if (t == 1) {  // ||X||_F^2 in fp64 (read at the checks)
+      double fro = 0.0;
+#pragma unroll
+      for (int m = 0; m < 8; ++m)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const float4 v = xr[m][h];
+          fro += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
+        }
+#pragma unroll
+      for (int m = 32; m >= 1; m >>= 1) fro += __shfl_xor(fro, m);
+      if (lane == 0) sR[32 + w] = fro;
+      pin_x();
+    }
+    lds_barrier();
+    T1_MARK(1);
+    {  // Y = X^T U
+      float acc[32];  // [column 4 h + e][p]
+      fresh_map();
+#pragma unroll
+      for (int q = 0; q < 32; ++q) acc[q] = 0.f;
+#pragma unroll
+      for (int m = 0; m < 8; ++m) {
+        const float4 uv = *reinterpret_cast<const float4*>(sU + uoff(a + 16 * m));
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const float xs[4] = {xr[m][h].x, xr[m][h].y, xr[m][h].z, xr[m][h].w};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int q = 4 * (4 * h + e);
+            acc[q + 0] = fmaf(xs[e], uv.x, acc[q + 0]);
+            acc[q + 1] = fmaf(xs[e], uv.y, acc[q + 1]);
+            acc[q + 2] = fmaf(xs[e], uv.z, acc[q + 2]);
+            acc[q + 3] = fmaf(xs[e], uv.w, acc[q + 3]);
+          }
+        }
+      }
+      // the wave's four a meet: lane bit 5 keeps chunk h, lane bit 4 columns 2 e' + {0, 1}
+      float a16[16], a8[8];
+      fresh_map();
+#pragma unroll
+      for (int q = 0; q < 16; ++q) a16[q] = rs_swap32(acc[q], acc[16 + q]);
+#pragma unroll
+      for (int q = 0; q < 8; ++q) a8[q] = rs_swap16(a16[q], a16[8 + q]);
+      float* dst = sP + w * 4 * N;
+      *reinterpret_cast<float4*>(dst + 4 * ppos(i0)) = make_float4(a8[0], a8[1], a8[2], a8[3]);
+      *reinterpret_cast<float4*>(dst + 4 * ppos(i0 + 1)) = make_float4(a8[4], a8[5], a8[6], a8[7]);
+    }
+    lds_barrier();
+    if (tid < N) {
+      const int pt = ppos(tid);
+      float4 s = *reinterpret_cast<const float4*>(sP + 4 * pt);
+#pragma unroll
+      for (int ww = 1; ww < 4; ++ww) {
+        const float4 o = *reinterpret_cast<const float4*>(sP + ww * 4 * N + 4 * pt);
+        s.x += o.x; s.y += o.y; s.z += o.z; s.w += o.w;
+      }
+      // Y in place of wave 0's partials. Thread i < N reads its rows of Y and Z back where
+      // it needs them (top1_kernel holds them in registers across the check).
+      *reinterpret_cast<float4*>(sP + 4 * tid) = s;
+    }
+    lds_barrier();
+    // Rayleigh-Ritz + residual test at rounds 2, 3, 4, then every second round
+    T1_MARK(2);
+    const bool check = t >= 2 && (t <= 4 || t % 2 == 0 || t == MAX_ROUNDS);  // uniform
+    // Gram sums in sR: [0, 10) Y^T Y (every round), [10, 20) Z^T Z, [20, 30) U^T U (checks)
+    if (check) {
+      gram_sums<30, true>(sP, sZt, sU, sR, tid);
+      double L[4][4], ri[4];
+      {
+        double M[4][4];
+        sym4(sR + 10, M);
+        chol4(M, L, ri);
+      }
+      double H[4][4];
+      sym4(sR + 20, H);
+      // C = L^-1 H L^-T with M = L L^T (dead basis columns: rows / columns of C zero)
+      double W[4][4];
+      float C[4][4];
+#pragma unroll
+      for (int cc = 0; cc < 4; ++cc) {  // W = L^-1 H, column by column
+#pragma unroll
+        for (int aa = 0; aa < 4; ++aa) {
+          double s = H[aa][cc];
+#pragma unroll
+          for (int l = 0; l < aa; ++l) s = fma(-L[aa][l], W[l][cc], s);
+          W[aa][cc] = s * ri[aa];
+        }
+      }
+#pragma unroll
+      for (int cc = 0; cc < 4; ++cc) {  // C = L^-1 W^T (lower triangle, mirrored)
+        double col[4];
+#pragma unroll
+        for (int aa = 0; aa < 4; ++aa) {
+          double s = W[cc][aa];
+#pragma unroll
+          for (int l = 0; l < aa; ++l) s = fma(-L[aa][l], col[l], s);
+          col[aa] = s * ri[aa];
+        }
+#pragma unroll
+        for (int aa = cc; aa < 4; ++aa) C[aa][cc] = C[cc][aa] = (float)col[aa];
+      }
+      // L and 1 / diag(L) wait in LDS (thread 0's copy: every thread holds the same) while
+      // the Jacobi sweeps run: 20 registers that the 128-register budget does not have there
+      if (tid == 0) {
+#pragma unroll
+        for (int l = 1; l < 4; ++l)
+#pragma unroll
+          for (int aa = 0; aa < l; ++aa) sR[46 + l * (l - 1) / 2 + aa] = L[l][aa];
+#pragma unroll
+        for (int n = 0; n < 4; ++n) sR[52 + n] = ri[n];
+      }
+      float Q[4][4];
+      jacobi4(C, Q);
+      // top Ritz pair and the second Ritz value, without indexing registers dynamically
+      float th1f = C[0][0], th2f = -3.0e38f, qt[4] = {Q[0][0], Q[1][0], Q[2][0], Q[3][0]};
+#pragma unroll
+      for (int aa = 1; aa < 4; ++aa) {
+        const bool gt = C[aa][aa] > th1f;
+        th2f = fmaxf(th2f, gt ? th1f : C[aa][aa]);
+        th1f = gt ? C[aa][aa] : th1f;
+#pragma unroll
+        for (int cc = 0; cc < 4; ++cc) qt[cc] = gt ? Q[cc][aa] : qt[cc];
+      }
+      lds_barrier();  // L, 1 / diag(L) of thread 0; sR reuse below
+      double q1[4];  // L^T q1 = qt (back substitution): v = Z q1 (unit norm up to fp32)
+#pragma unroll
+      for (int aa = 3; aa >= 0; --aa) {
+        double s = qt[aa];
+#pragma unroll
+        for (int l = aa + 1; l < 4; ++l) s = fma(-sR[46 + l * (l - 1) / 2 + aa], q1[l], s);
+        q1[aa] = s * sR[52 + aa];
+      }
+      double vi = 0.0, gv = 0.0;
+      if (tid < N) {
+        const float4 y4 = *reinterpret_cast<const float4*>(sP + 4 * tid);
+        const float y[4] = {y4.x, y4.y, y4.z, y4.w};
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+          vi = fma((double)sZt[zt(p, tid)], q1[p], vi);
+          gv = fma((double)y[p], q1[p], gv);  // (G v)_i
+        }
+      }
+      double rs[3] = {gv * vi, vi * vi, gv * gv};
+      bsum128<3>(rs, sR + 40, tid);
+      const double tr = (sR[32] + sR[33]) + (sR[34] + sR[35]);  // ||X||_F^2
+      // the fp64 Rayleigh quotient, residual and output-error test of top1_kernel
+      const double vv = fmax(rs[1], 1e-300);
+      const double th1 = rs[0] / vv;
+      const double res2 = fmax(rs[2] - th1 * rs[0], 0.0) / vv;
+      const double th2 = fmin((double)th2f, th1);
+      const double rest = fmax(tr - th1, 1e-4 * fmax(tr, 0.0));
+      const double f = fmin(1.0, rest / fmax(th1, 1e-300));
+      float tol = tolv;  // converted here, not held as a double across the loop
+      asm volatile("" : "+v"(tol));
+      const bool conv = sqrt(fmax(th1, 0.0) * res2) * f <= (double)tol * (th1 - th2) * sqrt(rest);
+      if (conv || t >= MAX_ROUNDS) {  // uniform
+#ifdef SPECENH_TOP1_STATS  // development build (tools/top1_stats.py): rounds in the flag word
+        if (flags && tid == 0) flags[b] = (conv ? 0 : 1) + 2 * t;
+#else
+        if (flags && tid == 0) flags[b] = conv ? 0 : 1;
+#endif
+        if (tid < N) vd[tid] = vi * rsq64<1>(vv);  // v / ||v|| (partials were read above)
+        T1_MARK(4);
+        break;
+      }
+      T1_MARK(4);
+    } else {
+      gram_sums<10, true>(sP, sZt, sU, sR, tid);
+    }
+    // Z = Y R^-1 (CholeskyQR, S = R^T R): each thread rewrites its own column of Zt
+    double L[4][4], ri[4], yd[4], zd[4];
+    {
+      double S[4][4];
+      sym4(sR, S);
+      chol4(S, L, ri);
+    }
+    if (tid < N) {
+      const float4 y4 = *reinterpret_cast<const float4*>(sP + 4 * tid);
+      yd[0] = y4.x, yd[1] = y4.y, yd[2] = y4.z, yd[3] = y4.w;
+      solve_row(L, ri, yd, zd);
+#pragma unroll
+      for (int p = 0; p < 4; ++p) sZt[zt(p, tid)] = (float)zd[p];
+    }
+    lds_barrier();
+    T1_MARK(3);
+  }
+  // ---- one power step in fp64 from the converged v, as top1_kernel: v <- X^T X v / ||..||,
+  // then u = X v
+  auto Xv = [&]() {  // ud = X vd: partial sums over the thread's 8 columns, DPP row sum
+    double s[8];
+    pin_x();
+    fresh_map();
+#pragma unroll
+    for (int m = 0; m < 8; ++m) s[m] = 0.0;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const double2 v01 = *reinterpret_cast<const double2*>(vd + 4 * c + 64 * h);
+      const double2 v23 = *reinterpret_cast<const double2*>(vd + 4 * c + 64 * h + 2);
+#pragma unroll
+      for (int m = 0; m < 8; ++m) {
+        const float4 x4 = xr[m][h];
+        s[m] = fma((double)x4.x, v01.x, s[m]);
+        s[m] = fma((double)x4.y, v01.y, s[m]);
+        s[m] = fma((double)x4.z, v23.x, s[m]);
+        s[m] = fma((double)x4.w, v23.y, s[m]);
+      }
+    }
+    double s4[4], s2[2];  // lane bits 3, 2, 1 scatter the rows, bit 0 is summed on both lanes
+#pragma unroll
+    for (int q = 0; q < 4; ++q) s4[q] = rs_dpp<0x128>(c3, s[q], s[4 + q]);
+#pragma unroll
+    for (int q = 0; q < 2; ++q) s2[q] = rs_dpp<0x141>(c2, s4[q], s4[2 + q]);
+    double s1 = rs_dpp<0x4E>(c1, s2[0], s2[1]);
+    s1 += dpp<0xB1, false>(s1);
+    if (!c0) ud[a + 16 * (c >> 1)] = s1;
+    lds_barrier();
+  };
+  lds_barrier();
+  Xv();
+  {  // w = X^T u: partial sums over the thread's 8 rows; v = w / ||w||
+    double s[8];  // [column 4 h + e]
+    pin_x();
+    fresh_map();
+#pragma unroll
+    for (int q = 0; q < 8; ++q) s[q] = 0.0;
+#pragma unroll
+    for (int m = 0; m < 8; ++m) {
+      const double u = ud[a + 16 * m];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const float4 x4 = xr[m][h];
+        s[4 * h + 0] = fma((double)x4.x, u, s[4 * h + 0]);
+        s[4 * h + 1] = fma((double)x4.y, u, s[4 * h + 1]);
+        s[4 * h + 2] = fma((double)x4.z, u, s[4 * h + 2]);
+        s[4 * h + 3] = fma((double)x4.w, u, s[4 * h + 3]);
+      }
+    }
+    double s4[4], s2[2];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) s4[q] = rs_swap32(s[q], s[4 + q]);
+#pragma unroll
+    for (int q = 0; q < 2; ++q) s2[q] = rs_swap16(s4[q], s4[2 + q]);
+    *reinterpret_cast<double2*>(wd + w * N + i0) = make_double2(s2[0], s2[1]);
+    lds_barrier();
+    const double wv = tid < N ? (wd[tid] + wd[N + tid]) + (wd[2 * N + tid] + wd[3 * N + tid]) : 0.0;
+    double nn[1] = {wv * wv};
+    bsum128<1>(nn, sR + 40, tid);
+    if (tid < N) vd[tid] = nn[0] > 0.0 ? wv * rsq64<1>(nn[0]) : 0.0;
+    lds_barrier();
+  }
+  Xv();
+  T1_MARK(5);
+  // ---- out = X - u v^T (fp64, rounded once to the output type), X from the registers
+  TO* Ob = out + b * ob;
+  pin_x();
+  fresh_map();
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int i = 4 * c + 64 * h;
+    const double2 v01 = *reinterpret_cast<const double2*>(vd + i);
+    const double2 v23 = *reinterpret_cast<const double2*>(vd + i + 2);
+#pragma unroll
+    for (int m = 0; m < 8; ++m) {
+      const int k = a + 16 * m;
+      const double u = ud[k];
+      const float4 xv = xr[m][h];
+      // rounded to fp32 first, as top1_kernel's outputs are: without the empty asm the two
+      // conversions of a 16-bit output are folded into one software fp64 -> fp16 rounding
+      // (other bits, and some 30 instructions per element)
+      float f[4] = {(float)fma(-u, v01.x, (double)xv.x), (float)fma(-u, v01.y, (double)xv.y),
+                    (float)fma(-u, v23.x, (double)xv.z), (float)fma(-u, v23.y, (double)xv.w)};
+      Out4<TO> o;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        asm volatile("" : "+v"(f[e]));
+        o.v[e] = to_out<TO>(f[e]);
+      }
+      if (k < Kr && i < r) *reinterpret_cast<Out4<TO>*>(Ob + (long long)k * osk + i) = o;
     }
   }
   T1_MARK(6);
@@ -3333,13 +3803,22 @@ hipError_t launch_top1_t(const float* A, long long batch, int m, int n, long lon
   if (attr != hipSuccess) return attr;
   const auto [xv, Kr, osk, osi] = orient(A, m, n, a_stride);
   const int r = std::min(m, n);
+  // rows of X and of the output contiguous (m >= n) and output rows aligned for the 4-element
+  // stores: X in registers, four workgroups per CU (SVD_TOP1_LDS forces the LDS kernel)
+  const bool reg = xv.si == 1 && osi == 1 && ((uintptr_t)out % (4 * sizeof(TO))) == 0 &&
+                   variant(V_SVD_TOP1_LDS) == 0;
   for (long long b0 = 0; b0 < batch; b0 += 1LL << 30) {  // one workgroup per matrix
     const long long nb = std::min<long long>(1LL << 30, batch - b0);
     XView xb = xv;
     xb.base = A + b0 * a_stride;
-    SPECENH_LAUNCH(top1_kernel<TO>, dim3((unsigned)nb), dim3(256), top1::LDS_BYTES, st, xb, Kr,
-                   r, 5e-6f, flags + b0, reinterpret_cast<TO*>(out) + b0 * (long long)m * n,
-                   (long long)m * n, osk, osi, nb, phase_clk ? phase_clk + 8 * b0 : nullptr);
+    TO* ob0 = reinterpret_cast<TO*>(out) + b0 * (long long)m * n;
+    long long* clk = phase_clk ? phase_clk + 8 * b0 : nullptr;
+    if (reg)
+      SPECENH_LAUNCH(top1_kernel_reg<TO>, dim3((unsigned)nb), dim3(256), 0, st, xb, Kr, r, 5e-6f,
+                     flags + b0, ob0, (long long)m * n, osk, nb, clk);
+    else
+      SPECENH_LAUNCH(top1_kernel<TO>, dim3((unsigned)nb), dim3(256), top1::LDS_BYTES, st, xb, Kr,
+                     r, 5e-6f, flags + b0, ob0, (long long)m * n, osk, osi, nb, clk);
   }
   return hipGetLastError();
 }

@@ -32,12 +32,22 @@ torch.cuda.synchronize()
 off = (B * r * r + B * r * K + B * K) * 4
 off = (off + 255) // 256 * 256
 flags = ws[off:off + 8 * B].view(torch.int32)
-print("flagged (top1_kernel, or the first subspace pass)", int(flags[:B].sum()), "of", B)
+print("flagged (top-1 kernel, or the first subspace pass)", int(flags[:B].sum()), "of", B)
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 res = {}
+# (label, SVD_NO_TOP1, SVD_TOP1_LDS): top1_kernel_reg (X in registers, default), top1_kernel
+# (X in LDS), and the Gram + subspace + recon pipeline. A library without the newer switch
+# (an older revision under tools/lib_ab.sh) times its one top-1 kernel under "top1".
+CASES = [("top1", 0, 0), ("top1 lds", 0, 1), ("pipeline", 1, 0)]
+try:
+    _lib.get_variant("SVD_TOP1_LDS")
+except Exception:
+    CASES = [c for c in CASES if not c[2]]
 for rnd in range(4):
-    for v in (0, 1):  # SVD_NO_TOP1: one-pass top1_kernel vs Gram + subspace + recon
-        _lib.set_variant("SVD_NO_TOP1", v)
+    for name, no_top1, lds in CASES:
+        _lib.set_variant("SVD_NO_TOP1", no_top1)
+        if len(CASES) == 3:
+            _lib.set_variant("SVD_TOP1_LDS", lds)
         svd.denoise_batch(S, out=A)
         e0.record()
         for _ in range(10):
@@ -45,8 +55,10 @@ for rnd in range(4):
         e1.record()
         e1.synchronize()
         if rnd:
-            res.setdefault(v, []).append(e0.elapsed_time(e1) / 10)
-for v, name in ((0, "top1"), (1, "pipeline")):
-    print(f"denoise_batch {B} x 128 x 128 -> fp16 [{name}]: {min(res[v]):.4f} ms "
-          f"(rounds {', '.join(f'{t:.4f}' for t in res[v])})")
+            res.setdefault(name, []).append(e0.elapsed_time(e1) / 10)
+for name, _, _ in CASES:
+    print(f"denoise_batch {B} x 128 x 128 -> fp16 [{name}]: {min(res[name]):.4f} ms "
+          f"(rounds {', '.join(f'{t:.4f}' for t in res[name])})")
 _lib.set_variant("SVD_NO_TOP1", 0)
+if len(CASES) == 3:
+    _lib.set_variant("SVD_TOP1_LDS", 0)

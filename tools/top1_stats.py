@@ -1,5 +1,6 @@
-"""Rounds top1_kernel needs on the C5 stream's matrices (development build with the round
-count in the flag word):
+"""Rounds and phase clocks of the top-1 kernel on the C5 stream's matrices (development build
+with the round count in the flag word): top1_kernel_reg by default, top1_kernel with
+SPECENH_SVD_TOP1_LDS=1 in the environment:
     tools/build_variant.sh t1stats svd_denoise.hip -DSPECENH_TOP1_STATS
     SPECENH_LIB=$PWD/tools/variants/libspecenh_t1stats.so python tools/top1_stats.py"""
 import ctypes
